@@ -17,7 +17,14 @@ A step = one full frame: every rank renders its rows (one HIP kernel launch via 
 resident in HBM) and the rows are gathered to rank 0 over RCCL.  The image is fixed, so N>1 is
 strong scaling.  Rank 0 prints ONE JSON line.
 
-`roofline` is the dominant kernel's VALU roofline (bound "valu": no GEMM-shaped work on this path,
+A plain run does only what `value` needs: set-up, W warm-up steps, the K timed steps, the line
+(`ms_per_step` = the timed region / K).  `--dump-outputs DIR` also writes the last timed step's
+gathered frame to DIR/image.npy; scene, camera and RNG are seeded, so the same arguments give the
+same inputs, and the same bits, in every run.  `--full` adds the side measurements and checks
+after the timed steps: `roofline`, `fast_f32`, `dropin_ms`, `cpu_baseline`, and at N > 1 the
+gather-alone timing (`ranks[].gather_ms`) and `rt_render_all_devices`.
+
+`roofline` (--full) is the dominant kernel's VALU roofline (bound "valu": no GEMM-shaped work on this path,
 DESIGN.md §5): achieved = the FLOPs the sample kernel executes per frame (exact in-kernel counts of
 one instrumented frame: 17 f64 FLOPs per ray-sphere candidate test, SURVEY §8(d)'s unit, plus 24 f32
 FLOPs per BVH node visit counted at half weight: a packed f32 fma issues in the cycles of one f64 fma)
@@ -227,7 +234,21 @@ def parse_args(argv=None):
                     help="at N > 1, skip rank 0's rt_render(n_gpus = 0) check over every visible GPU")
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks and join the process group, print one line, render nothing")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the side measurements and checks: the instrumented "
+                         "frame behind `roofline`, the f32 fast mode, the drop-in timings, the CPU baseline, "
+                         "and at N > 1 the gather-alone timing and the all-devices check (each can still be "
+                         "switched off with its --no-... option).  Without --full the run sets up, warms up, "
+                         "times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR as .npy files: "
+                         "image.npy, rank 0's gathered (H, W, 3) frame (float64; RGB8 output as float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def _free_port():
@@ -433,9 +454,9 @@ def run(args):
         torch.cuda.synchronize()
         if w == 0:
             first_ms = (time.perf_counter() - t_w) * 1e3
-    # one untimed instrumented frame: exact executed-work counts (sphere tests, BVH node visits)
+    # --full: one untimed instrumented frame: exact executed-work counts (sphere tests, BVH node visits)
     pstats = torch.zeros(rtzig.abi.RT_PROFILE_STATS_WORDS, dtype=torch.int64, device=dev)
-    if n_rows:
+    if n_rows and args.full:
         renderer.enable_profile(True)
         renderer.render_rows_async(cam.cam, out.data_ptr(), row0=row0, row_step=step, n_rows=n_rows,
                                    output=args.output, d_stats_ptr=pstats.data_ptr(),
@@ -462,6 +483,11 @@ def run(args):
     if grouped:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    # --dump-outputs: a host copy of the last timed frame now; at world 1 `img` is a view of a row
+    # buffer that the side measurements below render into again
+    dump = None
+    if args.dump_outputs and rank == 0 and img is not None:
+        dump = img.cpu().numpy().astype(np.float64 if args.output == "linear" else np.float32)
 
     t = torch.tensor([elapsed], dtype=torch.float64,
                      device=dev if args.dist_backend == "nccl" else "cpu")
@@ -484,10 +510,10 @@ def run(args):
         check = bool(got is not None and torch.equal(got, whole.cpu()))
         if not check:
             raise SystemExit("bench.py --check: the gathered frame differs from the whole-image render")
-    # N > 1: the gather alone, K times, bracketed like the timed region (the frame's other part)
+    # --full, N > 1: the gather alone, K times, bracketed like the timed region (the frame's other part)
     coll_dev = dev if args.dist_backend == "nccl" else "cpu"
     gather_ms = 0.0
-    if grouped:
+    if grouped and args.full:
         dist.barrier()
         torch.cuda.synchronize()
         tg = time.perf_counter()
@@ -505,16 +531,17 @@ def run(args):
     else:
         every = [mine]
     per_rank = [{"rank": int(v[0]), "rows": int(v[1]), "kernel_ms_per_frame": round(float(v[2]), 3),
-                 "reduce_ms_per_frame": round(float(v[3]), 3), "gather_ms": round(float(v[4]), 3),
+                 "reduce_ms_per_frame": round(float(v[3]), 3),
+                 "gather_ms": round(float(v[4]), 3) if args.full or not grouped else None,
                  "ms_per_step": round(float(v[5]), 3),
                  "workspace_GiB": round(float(v[6]) / 2**30, 3)} for v in (x.cpu() for x in every)]
     st = stats.cpu().tolist()
     rays_per_frame = st[0] / max(1, args.steps)
     samples_per_frame = st[1] / max(1, args.steps)
-    # side measurement (1 GPU only): RT_PRECISION_F32 fast mode on the same frame.  Statistical
+    # --full side measurement (1 GPU only): RT_PRECISION_F32 fast mode on the same frame.  Statistical
     # parity only (tests/test_fast_mode.py), so it is reported beside `value`, never as it.
     fast = None
-    if world == 1 and not args.no_fast and n_rows:
+    if args.full and world == 1 and not args.no_fast and n_rows:
         renderer.set_precision("f32")
         frame()
         finish()
@@ -537,10 +564,10 @@ def run(args):
     group_size = dist.get_world_size() if grouped else 1
     if grouped:
         dist.destroy_process_group()
-    # N > 1 on a multi-GPU node: the drop-in's own multi-device branch over every visible GPU
+    # --full, N > 1 on a multi-GPU node: the drop-in's own multi-device branch over every visible GPU
     # (rank 0 only, after the other ranks are done with their devices' work)
     device_check = None
-    if rank == 0 and world > 1 and not args.no_device_check:
+    if args.full and rank == 0 and world > 1 and not args.no_device_check:
         device_check = all_devices_check(ndev) if ndev > 1 else {"devices": ndev, "skipped": "one visible device"}
     if rank == 0:
         total_samples = W * H * spp * args.steps
@@ -606,7 +633,9 @@ def run(args):
                                  f"overlapped with the next frame's render ({NB} row buffers; "
                                  "rt_render_rows_async_split)")
                               if grouped else "")},
-            "roofline": {
+            "full": args.full,
+            # needs the instrumented frame's counts
+            "roofline": None if not args.full else {
                 "bound": "valu",
                 "kernel": kname,
                 "achieved": round(exec_tf, 3),
@@ -666,7 +695,11 @@ def run(args):
             **({"check": "gathered frame == whole-image render, bit for bit"} if check else {}),
             **({"rt_render_all_devices": device_check} if device_check is not None else {}),
         }
-        if world == 1 and not args.no_dropin and n_rows:
+        if dump is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "image.npy"), dump)
+            res["dumped_outputs"] = {"image": {"shape": list(dump.shape), "dtype": str(dump.dtype)}}
+        if args.full and world == 1 and not args.no_dropin and n_rows:
             times = dropin(cam, local_dev)
             one = dropin_one_shot(W, spp, args.aspect)
             res["dropin_ms"] = {
@@ -681,7 +714,7 @@ def run(args):
                         "rt_render(n_gpus=1) call inside this bench process, whose HIP runtime is already "
                         "up (context, scene + BVH upload, workspace, render, D2H of f64 linear); warm = "
                         "later calls on the cached context and scene"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(W, args.aspect, args.cpu_spp)
             res["speedup_vs_cpu_baseline"] = round(value / res["cpu_baseline"]["value"], 1)
         print(json.dumps(res), flush=True)

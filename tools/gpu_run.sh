@@ -10,7 +10,7 @@
 # Steps (environment knobs in brackets):
 #   smoke      __graft_entry__.smoke()
 #   tests      pytest -m gpu, one process, per-test limits                       [PYTEST_ARGS]
-#   bench      the default bench line                                            [BENCH_ARGS]
+#   bench      the bench line with every side measurement (bench.py --full)      [BENCH_ARGS]
 #   kprof      instrumented counts of one 100-spp config-4 frame, wave- and lane-level per region
 #              (tools/kprofile.py; then here: python tools/region_table.py <kprof.json>)  [KPROF_ARGS]
 #   profile    rocprofv3 kernel trace + separate PMC passes (tools/profile.sh)
@@ -43,7 +43,7 @@ for step in "$@"; do
   case $step in
     smoke)   run smoke 200 python3 -u -c "import __graft_entry__ as g; g.smoke()" ;;
     tests)   run gputest 900 python3 -u -m pytest tests -m gpu -x -v --timeout 150 --timeout-method thread $PYTEST_ARGS ;;
-    bench)   run bench 300 python3 -u bench.py $BENCH_ARGS ;;
+    bench)   run bench 300 python3 -u bench.py --full $BENCH_ARGS ;;
     kprof)   run kprof 200 python3 -u tools/kprofile.py --spp 100 --variants bvh --out "gpurun_out/kprof_$T.json" $KPROF_ARGS ;;
     profile) TAG=$T bash tools/profile.sh || exit $? ;;
     ab)      run ab_full 300 python3 -u tools/ab_libs.py $AB --spp ${SPP:-100} --rounds ${ROUNDS:-7}

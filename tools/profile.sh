@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 TAG=${TAG:-r02}
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-BENCH=${BENCH:-"bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-dropin"}
+BENCH=${BENCH:-"bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-dropin"}
 PMC_BENCH=${PMC_BENCH:-"bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-fast --no-dropin"}
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- python3 $BENCH > "$OUT/trace_bench.json" 2> "$OUT/trace.err" || exit $?
 echo "trace ok"
