@@ -11,19 +11,24 @@
  * Compiled with -ffp-contract=off so every f64 operation rounds exactly where the Zig code does
  * (Zig's default float mode is strict: no contraction, ordered @reduce(.Add)).
  *
- * Two render modes:
+ * Three render modes:
  *   A  (oracle_render_a)  the reference's single sequential Xoshiro256++ stream shared by the
  *      scene generator and the camera (Scene.zig:29-38).  PINNED: reproduces
  *      test-files/chapter14.ppm byte-for-byte (tests/test_oracle.py).
  *   B  (oracle_render_b)  identical arithmetic, but every (pixel, sample) draws from its own
  *      Xoshiro256++ stream keyed by rt_sample_key() — the GPU's RNG layout.  The GPU must match
  *      B bit-for-bit.
+ *   F  (oracle_render_f)  the per-sample reference of the GPU's f32 fast mode: the fast-mode sample
+ *      stream of DESIGN.md §5.6 (24-bit uniforms, paired draws) fed to the reference's operations,
+ *      written once over a real type and instantiated in double (the reference) and in float (the
+ *      yardstick for what f32 rounding alone does).  Neither models the GPU's bits.
  *
  * Third-party algorithm restated (not under /root/reference): Zig 0.14 std.Random —
  * DefaultPrng = Xoshiro256++ (std/Random/Xoshiro256.zig), seeded by SplitMix64
  * (std/Random/SplitMix64.zig), Random.float(f64) (std/Random.zig), std.math.pow(f64,x,5)
  * (std/math/pow.zig, frexp/repeated squaring), std.math.degreesToRadians (std/math.zig).
  */
+#ifndef ORACLE_F_BODY /* the file includes itself twice for mode F's body, at its end */
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -655,3 +660,314 @@ EXPORT int oracle_render_book(int chapter, uint32_t width, double ratio, uint8_t
     if (height_out) *height_out = (uint32_t)h;
     return 0;
 }
+
+/* ------------------------------------------------------------------------------------------------
+ * Mode F: the per-sample reference of fast mode (DESIGN.md §5.6 "Sample-stream contract").
+ * The body below (after #else) is compiled twice, once per real type.
+ * ---------------------------------------------------------------------------------------------- */
+/* wide: every uniform is one Random.float(f64) draw as in mode B (no 24-bit cut, no pairing) — F's
+ * arithmetic on B's stream, which pins F against B (oracle_render_f_wide); never the GPU's layout */
+typedef struct { xoshiro g; uint64_t draws; int wide; } fstream;
+static inline uint64_t f_word(fstream* s) { s->draws++; return xoshiro_next(&s->g); }
+
+#define ORACLE_F_BODY
+#define R double
+#define FN(name) name##_64
+#define F_SQRT sqrt
+#define F_FABS fabs
+#define F_FMIN fmin
+#define F_FMAX fmax
+#include "rt_oracle.c"
+#undef R
+#undef FN
+#undef F_SQRT
+#undef F_FABS
+#undef F_FMIN
+#undef F_FMAX
+#define R float
+#define FN(name) name##_32
+#define F_SQRT sqrtf
+#define F_FABS fabsf
+#define F_FMIN fminf
+#define F_FMAX fmaxf
+#include "rt_oracle.c"
+#undef R
+#undef FN
+#undef F_SQRT
+#undef F_FABS
+#undef F_FMIN
+#undef F_FMAX
+#undef ORACLE_F_BODY
+
+static uint64_t f_last_draws; /* Xoshiro words consumed by the last oracle_render_f call */
+EXPORT uint64_t oracle_f_last_draws(void) { return f_last_draws; }
+
+/* Mode F: rows row0 + k*row_step, k < n_rows into out[k*W + i] (per-pixel averages, samples added
+ * in sample order in double, times pixelSamplesScale as camera.zig:136-141), like mode B.
+ * real_bits = 64: the reference (double, true divisions and sqrt); 32: the same code in float. */
+EXPORT int oracle_render_f(const rt_camera* cam, const rt_sphere* spheres, size_t n, int real_bits,
+                           uint32_t row0, uint32_t row_step, uint32_t n_rows, double* out,
+                           uint64_t* rays_out, int n_threads) {
+    if (real_bits != 64 && real_bits != 32) return RT_ERR_INVALID;
+    uint64_t rays = 0, draws = 0;
+    if (real_bits == 64) render_rows_64(cam, spheres, n, row0, row_step, n_rows, out, &rays, &draws, n_threads, 0);
+    else render_rows_32(cam, spheres, n, row0, row_step, n_rows, out, &rays, &draws, n_threads, 0);
+    f_last_draws = draws;
+    if (rays_out) *rays_out = rays;
+    return 0;
+}
+
+/* F's 64-bit instantiation on mode B's stream (one Random.float(f64) per uniform): differs from
+ * oracle_render_b only by the f32-rounded inputs and operation order, so the two agree to ~1e-6
+ * except where that moves a ray across a silhouette (tests/test_oracle.py). */
+EXPORT int oracle_render_f_wide(const rt_camera* cam, const rt_sphere* spheres, size_t n, uint32_t row0,
+                                uint32_t row_step, uint32_t n_rows, double* out, uint64_t* rays_out,
+                                int n_threads) {
+    uint64_t rays = 0, draws = 0;
+    render_rows_64(cam, spheres, n, row0, row_step, n_rows, out, &rays, &draws, n_threads, 1);
+    if (rays_out) *rays_out = rays;
+    return 0;
+}
+
+#else /* ORACLE_F_BODY: mode F over the real type R; FN(x) suffixes the instantiation ---------- */
+
+typedef struct { R x, y, z; } FN(fv);
+#define FV FN(fv)
+static inline FV FN(fmk)(R x, R y, R z) { FV r = {x, y, z}; return r; }
+static inline FV FN(fadd)(FV a, FV b) { return FN(fmk)(a.x + b.x, a.y + b.y, a.z + b.z); }
+static inline FV FN(fsub)(FV a, FV b) { return FN(fmk)(a.x - b.x, a.y - b.y, a.z - b.z); }
+static inline FV FN(fmul)(FV a, FV b) { return FN(fmk)(a.x * b.x, a.y * b.y, a.z * b.z); }
+static inline FV FN(fneg)(FV a) { return FN(fmk)(-a.x, -a.y, -a.z); }
+static inline FV FN(fmuls)(FV a, R s) { return FN(fmk)(a.x * s, a.y * s, a.z * s); }            /* vec.zig:35 */
+static inline R FN(fdot)(FV a, FV b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }          /* vec.zig:114 */
+static inline R FN(flen_sq)(FV a) { return FN(fdot)(a, a); }                                   /* vec.zig:51 */
+static inline FV FN(funit)(FV a) { return FN(fmuls)(a, (R)1 / F_SQRT(FN(flen_sq)(a))); }      /* vec.zig:126, 39-45 */
+static inline FV FN(freflect)(FV v, FV n) {                                                    /* vec.zig:103 */
+    return FN(fsub)(v, FN(fmuls)(n, (R)2 * FN(fdot)(v, n)));
+}
+static inline FV FN(frefract)(FV v, FV n, R eta) {                                             /* vec.zig:107-112 */
+    const R cos_t = F_FMIN(-FN(fdot)(v, n), (R)1);
+    const FV r_perp = FN(fmuls)(FN(fadd)(v, FN(fmuls)(n, cos_t)), eta);
+    return FN(fsub)(r_perp, FN(fmuls)(n, F_SQRT(F_FABS((R)1 - FN(flen_sq)(r_perp)))));
+}
+static inline int FN(fnear_zero)(FV v) { return v.x < (R)1e-8 && v.y < (R)1e-8 && v.z < (R)1e-8; } /* vec.zig:26 */
+
+/* §5.6: a uniform is the top 24 bits of a word; a paired draw takes the top 24 bits of each
+ * 32-bit half of ONE word, high half first.  k * 2^-24 and 2u - 1 are exact in float. */
+static inline R FN(funiform)(fstream* s) {
+    if (s->wide) return (R)rd(&s->g);
+    return (R)(uint32_t)(f_word(s) >> 40) * (R)0x1p-24;
+}
+static inline void FN(funiform2)(fstream* s, R* a, R* b) {
+    if (s->wide) {
+        *a = (R)rd(&s->g);
+        *b = (R)rd(&s->g);
+        return;
+    }
+    const uint64_t w = f_word(s);
+    *a = (R)(uint32_t)(w >> 40) * (R)0x1p-24;
+    *b = (R)((uint32_t)w >> 8) * (R)0x1p-24;
+}
+static inline R FN(fpm1)(R u) { return (R)2 * u - (R)1; } /* randomDoubleRange(-1, 1) util.zig:20-22 */
+
+/* Vec.randomUnitVec (vec.zig:71-80): a trip is one paired draw (x, y) plus one single draw (z),
+ * accepted when 1e-30 < |p|^2 <= 1 (§5.6; the reference's bound is 1e-160 in f64) */
+static inline FV FN(frandom_unit_vec)(fstream* s) {
+    for (;;) {
+        R x, y;
+        FN(funiform2)(s, &x, &y);
+        x = FN(fpm1)(x);
+        y = FN(fpm1)(y);
+        const R z = FN(fpm1)(FN(funiform)(s));
+        const R ls = (x * x + y * y) + z * z;
+        if ((R)1e-30 < ls && ls <= (R)1) {
+            const R l = F_SQRT(ls);
+            return FN(fmk)(x / l, y / l, z / l); /* true division, vec.zig:77 */
+        }
+    }
+}
+
+/* One sphere record of fast mode (§5.6): centre, r^2, 1/r, albedo, fuzz, ior, 1/ior and Schlick's
+ * r0 per face are computed in f64 from the rt_sphere and rounded to f32; a huge sphere (r^2 >= 1e4
+ * or |c|_1 >= 1e4) keeps its f64 centre and r^2 for the hit test, which runs in double. */
+typedef struct {
+    FV c;
+    R r2, inv_r, fuzz, ior, inv_ior, r0_front, r0_back;
+    FV albedo;
+    uint32_t kind;
+    int huge;
+    double hc[3], hr2;
+} FN(fsphere);
+#define FS FN(fsphere)
+
+static FS* FN(fload_spheres)(const rt_sphere* s, size_t n) {
+    FS* o = (FS*)malloc(sizeof(FS) * (n ? n : 1));
+    for (size_t k = 0; k < n; k++) {
+        const double r = s[k].radius > 0 ? s[k].radius : 0; /* Sphere.init @max(0, r) sphere.zig:21 */
+        const double ior = s[k].refraction_index, inv_ior = 1.0 / ior;
+        double r0f = (1 - inv_ior) / (1 + inv_ior), r0b = (1 - ior) / (1 + ior); /* material.zig:106-108 */
+        r0f *= r0f;
+        r0b *= r0b;
+        o[k].c = FN(fmk)((R)(float)s[k].center[0], (R)(float)s[k].center[1], (R)(float)s[k].center[2]);
+        o[k].r2 = (R)(float)(r * r);
+        o[k].inv_r = (R)(float)(1.0 / r);
+        o[k].albedo = FN(fmk)((R)(float)s[k].albedo[0], (R)(float)s[k].albedo[1], (R)(float)s[k].albedo[2]);
+        o[k].fuzz = (R)(float)s[k].fuzz;
+        o[k].ior = (R)(float)ior;
+        o[k].inv_ior = (R)(float)inv_ior;
+        o[k].r0_front = (R)(float)r0f;
+        o[k].r0_back = (R)(float)r0b;
+        o[k].kind = s[k].material;
+        o[k].hc[0] = s[k].center[0]; o[k].hc[1] = s[k].center[1]; o[k].hc[2] = s[k].center[2];
+        o[k].hr2 = r * r;
+        o[k].huge = !(o[k].hr2 < 1e4 && fabs(o[k].hc[0]) + fabs(o[k].hc[1]) + fabs(o[k].hc[2]) < 1e4);
+    }
+    return o;
+}
+
+/* HittableList.hit (hittable.zig:64-77) over Sphere.hit (sphere.zig:26-42) in R; huge spheres in
+ * double on the ray's values (§5.6).  The far root is tried when the near one is not beyond t_min
+ * (sphere.zig:35-41; a near root beyond `closest` has a far root beyond it too). */
+static inline long FN(fworld_hit)(const FS* sp, size_t n, FV o, FV d, R t_min, R t_max, R* t_out) {
+    long best = -1;
+    R closest = t_max;
+    const R a = FN(flen_sq)(d);
+    const double dx = d.x, dy = d.y, dz = d.z;
+    const double a64 = (dx * dx + dy * dy) + dz * dz;
+    for (size_t k = 0; k < n; k++) {
+        if (sp[k].huge) {
+            const double cx = sp[k].hc[0] - (double)o.x, cy = sp[k].hc[1] - (double)o.y, cz = sp[k].hc[2] - (double)o.z;
+            const double h = (dx * cx + dy * cy) + dz * cz;
+            const double c = ((cx * cx + cy * cy) + cz * cz) - sp[k].hr2;
+            const double disc = h * h - a64 * c;
+            if (disc < 0) continue;
+            const double sq = sqrt(disc);
+            double ts = (h - sq) / a64;
+            if (!((double)t_min < ts)) ts = (h + sq) / a64;
+            if (!((double)t_min < ts && ts < (double)closest)) continue;
+            closest = (R)ts;
+            best = (long)k;
+            continue;
+        }
+        const FV oc = FN(fsub)(sp[k].c, o);
+        const R h = FN(fdot)(d, oc);
+        const R c = FN(flen_sq)(oc) - sp[k].r2;
+        const R disc = h * h - a * c;
+        if (disc < 0) continue;
+        const R sq = F_SQRT(disc);
+        R ts = (h - sq) / a;
+        if (!(t_min < ts)) ts = (h + sq) / a;
+        if (!(t_min < ts && ts < closest)) continue;
+        closest = ts;
+        best = (long)k;
+    }
+    *t_out = closest;
+    return best;
+}
+
+/* getRay (camera.zig:187-215) then rayColor (camera.zig:148-183) with Material.scatter
+ * (material.zig:27-110) for one (pixel, sample) stream; camera constants rounded to f32 (§5.6) */
+static FV FN(fsample)(const FS* sp, size_t n, const rt_camera* c, uint32_t i, uint32_t j, fstream* s,
+                      uint64_t* rays) {
+#define CAM3(f) FN(fmk)((R)(float)c->f[0], (R)(float)c->f[1], (R)(float)c->f[2])
+    const FV center = CAM3(center), p0 = CAM3(pixel0), du = CAM3(du), dv = CAM3(dv);
+    const FV ddu = CAM3(defocus_disk_u), ddv = CAM3(defocus_disk_v);
+#undef CAM3
+    const R t_min = (R)(float)c->t_min, t_max = (R)(float)c->t_max;
+    /* sampleSquare (camera.zig:203-209): one paired draw */
+    R ox, oy;
+    FN(funiform2)(s, &ox, &oy);
+    ox -= (R)0.5;
+    oy -= (R)0.5;
+    const FV ps = FN(fadd)(FN(fadd)(p0, FN(fmuls)(du, (R)i + ox)), FN(fmuls)(dv, (R)j + oy));
+    FV orig = center;
+    if (!((float)c->defocus_angle <= 0)) { /* defocusDiskSample (camera.zig:212-215) */
+        R x, y;
+        for (;;) { /* randomInUnitDisk (vec.zig:82-92): one paired draw a trip */
+            FN(funiform2)(s, &x, &y);
+            x = FN(fpm1)(x);
+            y = FN(fpm1)(y);
+            if (x * x + y * y < (R)1) break;
+        }
+        orig = FN(fadd)(FN(fadd)(center, FN(fmuls)(ddu, x)), FN(fmuls)(ddv, y));
+    }
+    FV dir = FN(fsub)(ps, orig);
+    FV att = FN(fmk)(1, 1, 1);
+    for (uint32_t b = 0; b < c->bounce_max; b++) {
+        R t;
+        (*rays)++;
+        const long k = FN(fworld_hit)(sp, n, orig, dir, t_min, t_max, &t);
+        if (k < 0) { /* sky (camera.zig:171-177) */
+            const R a = (R)0.5 * (FN(funit)(dir).y + (R)1);
+            const FV sky = FN(fadd)(FN(fmuls)(FN(fmk)(1, 1, 1), (R)1 - a),
+                                    FN(fmuls)(FN(fmk)((R)0.5, (R)0.7, (R)1), a));
+            return FN(fmul)(att, sky);
+        }
+        const FS* q = &sp[k];
+        /* hit record (sphere.zig:44-53) */
+        const FV p = FN(fadd)(orig, FN(fmuls)(dir, t));
+        const FV outward = FN(fmuls)(FN(fsub)(p, q->c), q->inv_r);
+        const int front = FN(fdot)(dir, outward) < 0;
+        const FV nrm = front ? outward : FN(fneg)(outward);
+        if (q->kind == RT_LAMBERTIAN) { /* material.zig:27-39 */
+            dir = FN(fadd)(nrm, FN(frandom_unit_vec)(s));
+            if (FN(fnear_zero)(dir)) dir = nrm;
+            att = FN(fmul)(att, q->albedo);
+        } else if (q->kind == RT_METAL) { /* material.zig:55-68 */
+            const FV refl = FN(funit)(FN(freflect)(dir, nrm));
+            dir = FN(fadd)(refl, FN(fmuls)(FN(frandom_unit_vec)(s), q->fuzz));
+            if (!(FN(fdot)(dir, nrm) > 0)) return FN(fmk)(0, 0, 0);
+            att = FN(fmul)(att, q->albedo);
+        } else { /* dielectric, material.zig:82-110 */
+            const R ri = front ? q->inv_ior : q->ior;
+            const FV ud = FN(funit)(dir);
+            const R cos_t = F_FMIN(-FN(fdot)(ud, nrm), (R)1);
+            const R sin_t = F_SQRT(F_FMAX((R)1 - cos_t * cos_t, (R)0));
+            const int cannot = ri * sin_t > (R)1;
+            const R r0 = front ? q->r0_front : q->r0_back;
+            const R x1 = (R)1 - cos_t, x2 = x1 * x1;
+            const R approx = r0 + ((R)1 - r0) * (x1 * (x2 * x2)); /* std.math.pow(x, 5), see zig_pow5 */
+            /* short-circuit `or` (material.zig:94): one uniform, drawn only when it can refract */
+            if (cannot || approx > FN(funiform)(s)) dir = FN(freflect)(ud, nrm);
+            else dir = FN(frefract)(ud, nrm, ri);
+        }
+        orig = p;
+    }
+    return FN(fmk)(0, 0, 0); /* camera.zig:181 */
+}
+
+static void FN(render_rows)(const rt_camera* cam, const rt_sphere* spheres, size_t n, uint32_t row0,
+                            uint32_t row_step, uint32_t n_rows, double* out, uint64_t* rays_out,
+                            uint64_t* draws_out, int n_threads, int wide) {
+    FS* sp = FN(fload_spheres)(spheres, n);
+    const uint32_t W = cam->image_width;
+    uint64_t rays = 0, draws = 0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : rays, draws) num_threads(n_threads > 0 ? n_threads : 1)
+    for (uint32_t k = 0; k < n_rows; k++) {
+        const uint32_t j = row0 + k * row_step;
+        for (uint32_t i = 0; i < W; i++) {
+            const uint64_t pixel = (uint64_t)j * W + i;
+            double sx = 0, sy = 0, sz = 0;
+            for (uint32_t smp = 0; smp < cam->samples_per_pixel; smp++) {
+                fstream st;
+                st.draws = 0;
+                st.wide = wide;
+                xoshiro_seed(&st.g, oracle_sample_key(cam->seed, pixel, smp)); /* mode B's key */
+                const FV col = FN(fsample)(sp, n, cam, i, j, &st, &rays);
+                sx += (double)col.x; sy += (double)col.y; sz += (double)col.z;
+                draws += st.draws;
+            }
+            double* o = out + 3 * ((size_t)k * W + i);
+            o[0] = sx * cam->pixel_samples_scale;
+            o[1] = sy * cam->pixel_samples_scale;
+            o[2] = sz * cam->pixel_samples_scale;
+        }
+    }
+    free(sp);
+    *rays_out = rays;
+    *draws_out = draws;
+}
+#undef FV
+#undef FS
+
+#endif /* ORACLE_F_BODY */

@@ -377,6 +377,14 @@ bool boundable(const rt_sphere& s) {
     return std::isfinite(r) && m < 1e30;
 }
 
+// The f64 side of fast mode's split (always_f32 in rt_kernel.hip): r^2 >= 1e4 or
+// |c|_1 >= 1e4, where an f32 sphere test no longer resolves t_min.  The negation of the kernel's
+// f32 condition, so a NaN lands on the f64 side in both.
+bool f32_unsafe(const rt_sphere& s) {
+    const double r = s.radius > 0 ? s.radius : 0.0;
+    return !(r * r < 1e4 && std::fabs(s.center[0]) + std::fabs(s.center[1]) + std::fabs(s.center[2]) < 1e4);
+}
+
 }  // namespace
 
 double scene_extent(const rt_sphere* s, size_t n) {
@@ -447,6 +455,19 @@ Bvh build(const rt_sphere* spheres, size_t n, double origin_bound, const std::ve
         for (size_t i = 0; i < B.prims.size(); i++) {
             if (drop[i]) always.push_back(B.prims[i].sphere);
             else keep.push_back(B.prims[i]);
+        }
+        B.prims.swap(keep);
+    }
+    // Fast mode tests a sphere in f64 only on the always-list (always_f32's split); its leaf test is
+    // f32.  A sphere on the f64 side of that split must therefore never sit in a leaf, whatever the
+    // criteria above decide (they skip scenes of at most kLeafMax spheres and keep at most kMaxBig):
+    // chapter 9's r = 100 ground, in a leaf, was re-hit by grazing rays leaving it, which then
+    // scattered inside it to the bounce limit (+0.7% rays, tests/test_fast_oracle.py).
+    {
+        std::vector<Prim> keep;
+        for (const Prim& p : B.prims) {
+            if (f32_unsafe(spheres[p.sphere])) always.push_back(p.sphere);
+            else keep.push_back(p);
         }
         B.prims.swap(keep);
     }

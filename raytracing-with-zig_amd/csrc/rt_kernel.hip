@@ -168,10 +168,16 @@ __device__ __forceinline__ f3 sub(f3 a, f3 b) { return f3{a.x - b.x, a.y - b.y, 
 __device__ __forceinline__ f3 mul(f3 a, f3 b) { return f3{a.x * b.x, a.y * b.y, a.z * b.z}; }
 __device__ __forceinline__ f3 neg(f3 a) { return f3{-a.x, -a.y, -a.z}; }
 __device__ __forceinline__ f3 muls(f3 a, float s) { return f3{a.x * s, a.y * s, a.z * s}; }
+// One product rounded and two fused, in a fixed order.  Written as a plain sum under contract(fast),
+// the backend chose per instantiation which product of a sum of products to fuse (here, in the
+// sphere tests' h, c and disc, and in the trip's |p|^2): the instrumented ring kernel's image
+// differed from the plain one's in the last bit (tests/test_fast_oracle.py).  A sum with one product
+// has one fused form, so the rest of fast mode stays with the pragma.
 __device__ __forceinline__ float dot(f3 a, f3 b) {
-#pragma clang fp contract(fast)
-    return a.x * b.x + a.y * b.y + a.z * b.z;
+    return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x));
 }
+// h^2 - a c of the sphere tests, likewise
+__device__ __forceinline__ float disc_of(float h, float a, float c) { return __builtin_fmaf(h, h, -(a * c)); }
 __device__ __forceinline__ float len_sq(f3 a) { return dot(a, a); }
 __device__ __forceinline__ f3 unit(f3 a) { return muls(a, __builtin_amdgcn_rsqf(len_sq(a))); }
 __device__ __forceinline__ f3 reflect(f3 v, f3 n) { return sub(v, muls(n, 2.0f * dot(v, n))); }
@@ -751,10 +757,10 @@ struct BvhWalker {
         for (uint32_t q = 0; q < n_always; ++q) {
             const GeoRec s = ageo[q];
             if (s.r2 < 1e4 && __builtin_fabs(s.cx) + __builtin_fabs(s.cy) + __builtin_fabs(s.cz) < 1e4) {
-                const float fx = (float)s.cx - r.orig.x, fy = (float)s.cy - r.orig.y, fz = (float)s.cz - r.orig.z;
-                const float h = r.dir.x * fx + r.dir.y * fy + r.dir.z * fz;
-                const float c = (fx * fx + fy * fy + fz * fz) - (float)s.r2;
-                const float disc = h * h - fa * c;
+                const fm::f3 oc = fm::mk((float)s.cx - r.orig.x, (float)s.cy - r.orig.y, (float)s.cz - r.orig.z);
+                const float h = fm::dot(r.dir, oc);
+                const float c = fm::len_sq(oc) - (float)s.r2;
+                const float disc = fm::disc_of(h, fa, c);
                 if (disc >= 0) {
                     const float sq = __builtin_sqrtf(disc), ia = __builtin_amdgcn_rcpf(fa);
                     float ts = (h - sq) * ia;
@@ -791,10 +797,10 @@ struct BvhWalker {
 #pragma unroll
         for (int u = 0; u < kLeafBvh; ++u) {
             const LeafGeo s = lf->g[u];
-            const float cx = (float)s.cx - r.orig.x, cy = (float)s.cy - r.orig.y, cz = (float)s.cz - r.orig.z;
-            const float h = r.dir.x * cx + r.dir.y * cy + r.dir.z * cz;
-            const float c = (cx * cx + cy * cy + cz * cz) - (float)s.r2;
-            const float disc = h * h - a * c;
+            const fm::f3 oc = fm::mk((float)s.cx - r.orig.x, (float)s.cy - r.orig.y, (float)s.cz - r.orig.z);
+            const float h = fm::dot(r.dir, oc);
+            const float c = fm::len_sq(oc) - (float)s.r2;
+            const float disc = fm::disc_of(h, a, c);
             if (disc >= 0) {
                 const float sq = __builtin_sqrtf(disc);
                 float ts = (h - sq) * inv_a;
@@ -1202,10 +1208,10 @@ __device__ __forceinline__ void trip_f32(Rng& g, bool wr, float& ux, float& uy, 
     fm::uniform2(g, ux, uy);
     ux = fm::pm1(ux);
     uy = fm::pm1(uy);
-    const float xy = ux * ux + uy * uy;
+    const float xy = __builtin_fmaf(uy, uy, ux * ux);  // fixed fused forms, see fm::dot
     if (wr) {
         uz = fm::pm1(fm::uniform(g));
-        uls = xy + uz * uz;
+        uls = __builtin_fmaf(uz, uz, xy);
     }
     // the flags are assigned by value on both sides: stores into got OR dgot through a selected
     // address kept both in scratch memory (8 bytes per lane, scratch_store_byte per trip)

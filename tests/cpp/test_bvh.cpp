@@ -106,6 +106,14 @@ static void run(const std::vector<rt_sphere>& s, const char* name, bool trained 
     for (uint32_t k : seen)
         if (k != rtbvh::kSentinel) count.at(k)++;
     for (size_t k = 0; k < s.size(); k++) CHECK(count[k] == 1, "%s: sphere %zu appears %d times", name, k, count[k]);
+    // fast mode's leaf test is f32: no leaf holds a sphere of the f64 side of its split
+    // (r^2 >= 1e4 or |c|_1 >= 1e4), whatever the scene's size
+    for (uint32_t k : seen) {
+        if (k == rtbvh::kSentinel) continue;
+        const double r = s[k].radius > 0 ? s[k].radius : 0.0;
+        const double c1 = std::fabs(s[k].center[0]) + std::fabs(s[k].center[1]) + std::fabs(s[k].center[2]);
+        CHECK(r * r < 1e4 && c1 < 1e4, "%s: sphere %u (r %g, |c|_1 %g) in a leaf", name, k, r, c1);
+    }
     check_boxes(b, s, 0);
     // the host traversal (training-ray sampler) finds the linear scan's closest sphere
     std::mt19937_64 rng(11);
@@ -139,6 +147,16 @@ int main() {
     {  // tiny scenes, including the single-sphere and two-sphere roots
         run({sph(0, 0, -1, 0.5)}, "one");
         run({sph(0, 0, -1, 0.5), sph(0, -100.5, -1, 100)}, "two");
+    }
+    {  // more huge spheres than kMaxBig, on both criteria of the split, among small ones
+        std::vector<rt_sphere> s;
+        for (int k = 0; k < 6; k++) s.push_back(sph(300.0 * k, -100.5, -1, 100 + k));
+        s.push_back(sph(-60, 30, -9900, 90));   // |c|_1 = 9990: an f32 test
+        s.push_back(sph(60, 30, -9920, 90));    // |c|_1 = 10010: f64
+        std::mt19937_64 own(5);  // leaves the other scenes' draws as they were
+        std::normal_distribution<double> M(0, 5);
+        for (int k = 0; k < 20; k++) s.push_back(sph(M(own), M(own), M(own), 0.3));
+        run(s, "many_huge");
     }
     {  // soup with duplicates, zero/negative radii, a huge sphere and an unboundable one
         std::vector<rt_sphere> s;

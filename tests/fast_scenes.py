@@ -1,0 +1,153 @@
+"""Cameras and scenes of the fast-mode per-sample oracle tests, and the one rule they apply.
+
+Shared by tests/test_oracle.py (CPU: oracle F's 32-bit instantiation against its 64-bit one) and
+tests/test_fast_oracle.py (GPU: the f32 fast mode against the same pair).  Everything is rendered at
+1 sample per pixel unless stated, so a pixel is one sample's colour.
+"""
+import numpy as np
+
+import rtzig
+from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtSphere
+
+THETAS = (1e-3, 1e-4, 1e-5)
+INPUT_CAP = 0.01  # share_F32(1e-3) every scene below must stay under (checked on the CPU)
+GPU_CAP = 0.02    # share_gpu(1e-3), whatever F32 says
+
+
+def final(depth, width=240, spp=1):
+    return rtzig.final_scene_camera(width=width, aspect_ratio=1.5, spp=spp, bounce_max=depth)
+
+
+def chapter13(width=240, spp=1):
+    return rtzig.chapter13_camera(width=width, spp=spp)
+
+
+def chapter9():
+    return rtzig.chapter9_camera(width=240, spp=1)
+
+
+def materials():
+    """The scene of test_gpu_parity.test_materials_and_degenerate_spheres: fuzz > 1 absorption, a
+    zero-radius sphere, an exact duplicate and inside-glass paths."""
+    scene = rtzig.Scene.init(0x1234)
+    scene.add((0, -100.5, -1), 100, RT_LAMBERTIAN, albedo=(0.8, 0.8, 0.0))
+    scene.add((0, 0, -1.2), 0.5, RT_METAL, albedo=(0.9, 0.9, 0.9), fuzz=1.7)
+    scene.add((-1, 0, -1), 0.5, RT_DIELECTRIC, refraction_index=1.5)
+    scene.add((-1, 0, -1), 0.4, RT_DIELECTRIC, refraction_index=1.0 / 1.5)
+    scene.add((1, 0, -1), 0.5, RT_METAL, albedo=(0.8, 0.6, 0.2), fuzz=0.0)
+    scene.add((1, 0, -1), 0.5, RT_LAMBERTIAN, albedo=(0.1, 0.1, 0.9))  # exact duplicate: never wins
+    scene.add((0, 1, -1), -0.3, RT_LAMBERTIAN)                          # radius clamps to 0
+    return (rtzig.Camera.builder(240, 16 / 9).setScene(scene).setDefocusAngle(2.0).setFocusDist(1.5)
+            .setViewport((0, 0.3, 0.5), (0, 0, -1), 70).setSamplesPerPixel(1).build())
+
+
+def ground(radius):
+    """Chapter 13's spheres on a ground of the given radius whose top stays at y = -0.5: at 99.9
+    the ground's r^2 < 1e4 (f32 sphere test), at 100.1 it is on the f64 side of the split."""
+    scene = rtzig.Scene.init(0xC0FFEE)
+    scene.add((0, -0.5 - radius, -1), radius, RT_LAMBERTIAN, albedo=(0.8, 0.8, 0.0))
+    scene.add((0, 0, -1.2), 0.5, RT_LAMBERTIAN, albedo=(0.1, 0.2, 0.5))
+    scene.add((-1, 0, -1), 0.5, RT_DIELECTRIC, refraction_index=1.5)
+    scene.add((-1, 0, -1), 0.4, RT_DIELECTRIC, refraction_index=1.0 / 1.5)
+    scene.add((1, 0, -1), 0.5, RT_METAL, albedo=(0.8, 0.6, 0.2), fuzz=0.3)
+    return (rtzig.Camera.builder(240, 16 / 9).setScene(scene).setDefocusAngle(1.0).setFocusDist(3.4)
+            .setViewport((-2, 2, 1), (0, 0, -1), 25).setSamplesPerPixel(1).build())
+
+
+def c1_straddle(depth=1):
+    """Two radius-90 spheres 9 900 units away whose |c|_1 is 9 990 (f32 test) and 10 010 (f64
+    test), behind three small spheres that make them always-list entries (10x the median box).
+    Depth 1 (primary visibility through both sides of the split): a |c|_1 of 1e4 needs a coordinate
+    of 3 333 or more, where an f32 hit point is known to 2.4e-4 or worse against t_min = 1e-3, so
+    rays leaving such a sphere re-hit it in any f32 arithmetic and share_F32(1e-3) is 3.8% at depth 2."""
+    scene = rtzig.Scene.init(0xFACADE)
+    scene.add((-60, 30, -9900), 90, RT_LAMBERTIAN, albedo=(0.8, 0.3, 0.3))
+    scene.add((60, 30, -9920), 90, RT_LAMBERTIAN, albedo=(0.3, 0.3, 0.8))
+    scene.add((-1.1, -0.8, -60), 0.5, RT_DIELECTRIC, refraction_index=1.5)
+    scene.add((0, -0.8, -60), 0.5, RT_METAL, albedo=(0.8, 0.8, 0.8), fuzz=0.1)
+    scene.add((1.1, -0.8, -60), 0.5, RT_LAMBERTIAN, albedo=(0.2, 0.7, 0.2))
+    return (rtzig.Camera.builder(240, 1.5).setScene(scene).setDefocusAngle(0.0).setFocusDist(10)
+            .setViewport((0, 0, 0), (0, 0, -1), 3).setSamplesPerPixel(1).setBounceMax(depth).build())
+
+
+def large():
+    """The 2600-sphere scene of test_gpu_parity.test_large_scene_global_memory_variant (more
+    spheres than the LDS holds), 96 wide at 2 spp.  Depth 3: its overlapping random spheres diverge
+    more than any other scene here, share_F32(1e-3) = 0.54% at depth 3, 0.93% at 4, 1.6% at 50."""
+    rng = np.random.default_rng(11)
+    n = 2600
+    arr = (RtSphere * n)()
+    arr[0] = RtSphere(center=D3(0, -1000, 0), radius=1000, material=RT_LAMBERTIAN, albedo=D3(0.5, 0.5, 0.5))
+    for k in range(1, n):
+        arr[k] = RtSphere(center=D3(*rng.uniform([-30, 0.1, -30], [30, 3, 30])),
+                          radius=float(rng.uniform(0.05, 0.3)), material=int(k % 3),
+                          albedo=D3(*rng.uniform(0, 1, 3)), fuzz=float(rng.uniform(0, 0.5)),
+                          refraction_index=1.5)
+    scene = rtzig.Scene.init(77)
+    scene.world = arr
+    return (rtzig.Camera.builder(96, 16 / 9).setScene(scene).setDefocusAngle(0.6).setFocusDist(10)
+            .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(2).setBounceMax(3).build())
+
+
+# name -> camera factory: every scene the GPU tests hold to the rule; the CPU test checks the input
+# condition share_F32(1e-3) <= INPUT_CAP on each.
+# More than one sample per pixel: a pixel average differs as soon as one of its samples diverges, so
+# the share grows with spp.  On the final scene share_F32(1e-3) is 1.1% (spp 3) and 4.7% (spp 17)
+# at depth 50, 0.26% and 1.6% at depth 2: spp 3 runs at depth 2, spp 17 at depth 1, and chapter 13
+# (0.30% at spp 17) carries spp 17 at depth 50.
+SCENES = {
+    "final_d1": lambda: final(1),
+    "final_d2": lambda: final(2),
+    "final_d50": lambda: final(50),
+    "chapter13": chapter13,
+    "chapter9": chapter9,
+    "materials": materials,
+    "ground_99.9": lambda: ground(99.9),
+    "ground_100.1": lambda: ground(100.1),
+    "c1_straddle": c1_straddle,
+    "large_2600": large,
+    "final_w64_spp3_d2": lambda: final(2, width=64, spp=3),
+    "final_w64_spp17_d1": lambda: final(1, width=64, spp=17),
+    "chapter13_w64_spp17": lambda: chapter13(width=64, spp=17),
+}
+
+
+def shares(x, ref):
+    """Share of pixels whose max-channel |x - ref| exceeds each theta of THETAS."""
+    d = np.abs(np.asarray(x) - ref).max(axis=-1).ravel()
+    return [float((d > th).mean()) for th in THETAS]
+
+
+def reference_pair(oracle, cam, threads=8):
+    """(F64 image, F64 rays, F32 image, F32 rays) of oracle mode F for a camera and its scene."""
+    f64, r64 = oracle.render_f(cam.cam, cam.scene.world, 64, threads=threads)
+    f32, r32 = oracle.render_f(cam.cam, cam.scene.world, 32, threads=threads)
+    return f64, r64, f32, r32
+
+
+def check_against_pair(gpu, rays_gpu, pair, label=""):
+    """The one rule: divergence, cap, paired bias, rays and finiteness of a fast-mode
+    render against the F64 / F32 reference pair.  Prints every figure before it asserts."""
+    f64, r64, f32, r32 = pair
+    assert gpu.shape == f64.shape
+    finite = bool(np.isfinite(gpu).all())
+    sg, sf = shares(gpu, f64), shares(f32, f64)
+    dg = (gpu - f64).reshape(-1, 3)
+    df = (f32 - f64).reshape(-1, 3)
+    n = dg.shape[0]
+    mean_g, mean_f = dg.mean(axis=0), df.mean(axis=0)
+    se = dg.std(axis=0, ddof=1) / np.sqrt(n)
+    print(f"FASTORACLE {label} n={n} share_gpu={sg} share_f32={sf} mean_gpu={mean_g.tolist()} "
+          f"mean_f32={mean_f.tolist()} se={se.tolist()} rays_gpu={rays_gpu} rays_f64={r64} rays_f32={r32} "
+          f"finite={finite}")
+    assert finite, "non-finite output"
+    assert sf[0] <= INPUT_CAP, f"input condition: share_F32(1e-3) = {sf[0]}"
+    for th, g, f in zip(THETAS, sg, sf):
+        assert g <= 2 * f + 0.001, f"divergence at theta={th}: gpu {g} vs F32 {f}"
+    assert sg[0] <= GPU_CAP, f"cap: share_gpu(1e-3) = {sg[0]}"
+    for c in range(3):
+        assert abs(mean_g[c]) <= 2 * abs(mean_f[c]) + 4 * se[c], \
+            f"paired bias, channel {c}: gpu {mean_g[c]} vs F32 {mean_f[c]}, se {se[c]}"
+    assert abs(rays_gpu - r64) <= 2 * abs(r32 - r64) + 0.002 * r64, \
+        f"rays: gpu {rays_gpu}, F64 {r64}, F32 {r32}"
+    return sg, sf

@@ -1,7 +1,8 @@
 """ctypes wrapper around oracle/liboracle.so — the CPU parity checker (test infrastructure only).
 
 Mode A = the reference's single sequential RNG stream (pinned to test-files/chapter14.ppm);
-mode B = same arithmetic, per-(pixel, sample) streams (the GPU's RNG layout).
+mode B = same arithmetic, per-(pixel, sample) streams (the GPU's RNG layout);
+mode F = the f32 fast mode's sample stream in double (reference) or float (yardstick).
 """
 import ctypes as C
 import os
@@ -26,6 +27,11 @@ class Oracle:
         L.oracle_render_a.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, P(C.c_uint64), dp, P(C.c_uint64)]
         L.oracle_render_b.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, C.c_uint32, C.c_uint32,
                                       C.c_uint32, dp, P(C.c_uint64), C.c_int]
+        L.oracle_render_f.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, C.c_int, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, dp, P(C.c_uint64), C.c_int]
+        L.oracle_f_last_draws.restype = C.c_uint64
+        L.oracle_render_f_wide.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, dp, P(C.c_uint64), C.c_int]
         L.oracle_to_rgb8.argtypes = [dp, C.c_size_t, P(C.c_uint8)]
         L.oracle_ppm_p6.argtypes = [P(C.c_uint8), C.c_uint32, C.c_uint32, P(C.c_uint8), C.c_size_t]
         L.oracle_ppm_p6.restype = C.c_size_t
@@ -80,6 +86,29 @@ class Oracle:
         rays = C.c_uint64()
         self.L.oracle_render_b(C.byref(cam), spheres, len(spheres), row0, row_step, n_rows,
                                out.ctypes.data_as(dp), C.byref(rays), threads)
+        return out, rays.value
+
+    def render_f(self, cam, spheres, real_bits=64, row0=0, row_step=1, n_rows=None, threads=1, draws=None):
+        """Mode F (fast mode's sample stream) in double (64) or float (32):
+        (per-pixel averages, rays).  draws: a dict that receives the Xoshiro words consumed."""
+        W, H = cam.image_width, cam.image_height
+        if n_rows is None:
+            n_rows = (H - row0 + row_step - 1) // row_step
+        out = np.zeros((n_rows, W, 3))
+        rays = C.c_uint64()
+        rc = self.L.oracle_render_f(C.byref(cam), spheres, len(spheres), real_bits, row0, row_step, n_rows,
+                                    out.ctypes.data_as(dp), C.byref(rays), threads)
+        assert rc == 0, rc
+        if draws is not None:
+            draws["words"] = self.L.oracle_f_last_draws()
+        return out, rays.value
+
+    def render_f_wide(self, cam, spheres, threads=1):
+        """Mode F's 64-bit arithmetic on mode B's stream (pins F against B; not the GPU's layout)."""
+        out = np.zeros((cam.image_height, cam.image_width, 3))
+        rays = C.c_uint64()
+        self.L.oracle_render_f_wide(C.byref(cam), spheres, len(spheres), 0, 1, cam.image_height,
+                                    out.ctypes.data_as(dp), C.byref(rays), threads)
         return out, rays.value
 
     def to_rgb8(self, lin):

@@ -204,3 +204,73 @@ def test_presets_statistically_match_reference_images(oracle, golden_dir, config
     floor = _box_rmse(A, B)
     assert np.abs(B.astype(np.float64).mean(axis=(0, 1)) - gold.astype(np.float64).mean(axis=(0, 1))).max() <= 1.0
     assert _box_rmse(B, gold) <= 1.5 * floor, (_box_rmse(B, gold), floor)
+
+
+# ---- oracle mode F: the per-sample reference of the f32 fast mode ---------------
+def test_mode_f_arithmetic_matches_mode_b_on_b_stream(oracle):
+    """F's 64-bit instantiation fed mode B's stream (render_f_wide: one Random.float(f64) per
+    uniform) restates the same operations as B from f32-rounded inputs, so the two agree within 1e-6
+    on every pixel except those where the ~1e-7 input rounding moves a ray across a silhouette:
+    none at depth 1, 0.03% at depth 2, 0.57% at depth 50 on the final scene (240x160, 1 spp),
+    capped at 1%.  (On F's own stream the two cannot be compared per pixel: B draws the two
+    sampleSquare offsets from two words, F from the halves of one.)"""
+    import fast_scenes as fs
+    for depth in (1, 2, 50):
+        cam = fs.final(depth)
+        b, rays_b = oracle.render_b(cam.cam, cam.scene.world, threads=8)
+        f, rays_f = oracle.render_f_wide(cam.cam, cam.scene.world, threads=8)
+        share = float((np.abs(b - f).max(axis=-1) > 1e-6).mean())
+        assert share <= 0.01, (depth, share)
+        assert abs(rays_b - rays_f) <= 0.002 * rays_b, (depth, rays_b, rays_f)
+
+
+def test_mode_f_stream_layout(oracle):
+    """§5.6's draw layout restated in numpy for the first draw of a sample: sampleSquare's x offset is
+    the top 24 bits of the high half of word 0, its y offset the top 24 bits of the low half.
+    Chapter 9's camera (no defocus) at depth 1 on sky pixels: the colour is the sky gradient
+    (camera.zig:171-177) of the ray through that sample point."""
+    import fast_scenes as fs
+    cam = fs.chapter9()
+    c = cam.cam
+    c.bounce_max = 1
+    f64, _ = oracle.render_f(c, cam.scene.world, 64)
+    r32 = lambda v: np.array([np.float32(x) for x in v], np.float64)
+    p0, du, dv, center = r32(c.pixel0), r32(c.du), r32(c.dv), r32(c.center)
+    for i, j in ((0, 0), (17, 3), (239, 0), (120, 20)):
+        w = int(oracle.random_u64(oracle.sample_key(c.seed, j * c.image_width + i, 0), 1)[0])
+        ox = (w >> 40) * 2.0 ** -24 - 0.5
+        oy = ((w & 0xFFFFFFFF) >> 8) * 2.0 ** -24 - 0.5
+        d = (p0 + du * (i + ox)) + dv * (j + oy) - center
+        a = 0.5 * (d[1] / np.sqrt(d @ d) + 1.0)
+        sky = (1.0 - a) * np.ones(3) + a * np.array([0.5, 0.7, 1.0])
+        assert np.abs(f64[j, i] - sky).max() < 1e-12, (i, j, f64[j, i], sky)
+
+
+def test_mode_f_instantiations_consume_the_same_draws(oracle):
+    """The 64- and 32-bit instantiations read the same stream: identical Xoshiro word and ray counts
+    where no rejection or branch sits within f32 rounding of its boundary (final scene at depth 1;
+    chapter 9, all Lambertian, at depth 50)."""
+    import fast_scenes as fs
+    for name in ("final_d1", "chapter9"):
+        cam = fs.SCENES[name]()
+        d64, d32 = {}, {}
+        _, r64 = oracle.render_f(cam.cam, cam.scene.world, 64, threads=8, draws=d64)
+        _, r32 = oracle.render_f(cam.cam, cam.scene.world, 32, threads=8, draws=d32)
+        assert d64["words"] == d32["words"] > cam.width * cam.height and r64 == r32, (name, d64, d32, r64, r32)
+
+
+def test_mode_f_inputs_stay_under_the_divergence_cap(oracle):
+    """The input condition of tests/test_fast_oracle.py, checked where it can fail with a clear
+    message: on every scene there, F32 differs from F64 by more than 1e-3 on at most 1% of the
+    pixels (and both are finite).  A scene that drifts over it is replaced, not tolerated."""
+    import fast_scenes as fs
+    for name, make in fs.SCENES.items():
+        cam = make()
+        f64, _, f32, _ = fs.reference_pair(oracle, cam)
+        assert np.isfinite(f64).all() and np.isfinite(f32).all(), name
+        share = fs.shares(f32, f64)
+        print(f"MODEF {name} {cam.width}x{cam.height} share_f32={share}")
+        assert share[0] <= fs.INPUT_CAP, f"{name}: share_F32(1e-3) = {share[0]} > {fs.INPUT_CAP}"
+    cam = fs.SCENES["final_d1"]()  # the depth-1 cases assert share_gpu(1e-5) directly: F32 == F64 here
+    f64, _, f32, _ = fs.reference_pair(oracle, cam)
+    assert np.abs(f32 - f64).max() <= 1e-6
