@@ -181,6 +181,44 @@ int rt_render_rows_async_split(rt_context* ctx, const rt_camera* cam, uint32_t o
 int rt_render_rows_async_deferred(rt_context* ctx, const rt_camera* cam, uint32_t output_format,
                                   uint32_t row0, uint32_t row_step, uint32_t n_rows,
                                   void* d_out, void* d_stats, void* stream, void* out_stream);
+/* ---- progressive rendering: sample ranges accumulated bit-exactly ------------------------------
+ * Renders samples [sample_begin, sample_begin + sample_count) of rows row0 + k*row_step, k < n_rows,
+ * and adds each pixel's colours, in sample order, to the UNSCALED running sums in DEVICE memory
+ * d_accum (n_rows*W pixels x 3 doubles).  sample_begin == 0 starts a new image: d_accum's previous
+ * contents are ignored and overwritten (it need not be initialised).  sample_begin > 0 continues
+ * from the sums a previous call left there.  cam->samples_per_pixel and pixel_samples_scale are
+ * not used.  Asynchronous on `stream`; d_stats as rt_render_rows_async.  One sample-kernel launch.
+ *
+ * Bits: the reference adds a pixel's samples strictly in sample order and scales once at the end
+ * (camera.zig:133-137), and a sample's stream key (seed, pixel, sample) does not depend on the
+ * sample count.  So for ANY split of [0, n) into consecutive calls on one d_accum, in either unit
+ * mode and in any mix of them, rt_accum_resolve(n) is bit-identical to rt_render_rows_async at
+ * samples_per_pixel = n (RT_PRECISION_F32 contexts: to the one-pass fast render at n), and the
+ * {rays, samples} the passes add to d_stats sum to the one-pass counts.  The accumulator is plain
+ * data: copied to the host and back (or into another buffer) it resumes exactly.  Passes on one
+ * d_accum must be ordered (one stream, or events); the caller keeps track of the samples done.
+ *
+ * sample_count == 0 or n_rows == 0: RT_OK, nothing is touched.  RT_ERR_INVALID: null ctx, cam or
+ * d_accum; a row range past the image; sample_begin + sample_count > 2^32 - 1.  RT_ERR_CAPACITY:
+ * too many work units, as rt_render_rows_async.
+ *
+ * Launch: a plain one-stream call — a pending deferred reduce pass runs first.  The unit mode is
+ * chosen from the pass's own size (P x sample_count x 24 B; RTZIG_UNIT_MODE forces it), and the BVH
+ * training from the pass's sample count (any tree gives the same bits).  In ring mode d_accum is
+ * the kernel's running-sum buffer itself; in direct mode the reduce pass adds to it.  Timing
+ * (rt_context_kernel_times*) and instrumented contexts (rt_context_enable_profile, 72-word d_stats)
+ * work as for rt_render_rows_async.  Every pass pays a launch's ramp and tail. */
+int rt_render_rows_accumulate(rt_context* ctx, const rt_camera* cam,
+                              uint32_t row0, uint32_t row_step, uint32_t n_rows,
+                              uint32_t sample_begin, uint32_t sample_count,
+                              void* d_accum, void* d_stats, void* stream);
+/* d_out[q] = d_accum[q] * (1.0 / n_samples) (camera.zig:284,137) for n_pixels pixels, linear f64
+ * (3 doubles per pixel) or the fused Color.toRgb (3 bytes); asynchronous on `stream`.  d_accum is
+ * not modified, so a caller can resolve a preview and go on accumulating.  n_pixels == 0: RT_OK.
+ * RT_ERR_INVALID: null ctx, d_accum or d_out; n_samples == 0; a bad output_format;
+ * n_pixels >= 2^32. */
+int rt_accum_resolve(rt_context* ctx, const void* d_accum, uint64_t n_pixels, uint32_t n_samples,
+                     uint32_t output_format, void* d_out, void* stream);
 /* Runs a pending deferred reduce pass (on the out_stream of the call that deferred it); no-op otherwise. */
 int rt_context_flush(rt_context* ctx);
 /* *pending = 1 if the last deferred call left its output pending (direct mode), else 0. */

@@ -99,6 +99,27 @@ struct UnitArgs {
     double scale;              // pixelSamplesScale
     FoldArgs fold;             // direct mode: a previous call's samples to fold in the tail (may be empty)
 };
+// Accumulate passes (rt_render_rows_accumulate: samples [b, b + n) added to the caller's accumulator;
+// DESIGN.md §5.7) run the SAME ring-mode kernels on other wave-uniform values — the ring kernels have
+// no code for them.  A pass is a launch over a window of the image's chunk sequence:
+//   - `sums` is the caller's accumulator, and the chunk table holds ABSOLUTE sample numbers
+//     (accum_schedule_kernel writes it, stream-ordered), so a lane's sample is the one its stream is
+//     keyed with;
+//   - n_chunks counts one chunk more than the pass renders, the next pass's first: the pass's last
+//     chunk hands its sums on (k + 1 < n_chunks) like any other and `out` is never written;
+//   - a pass that continues an image (b > 0) also counts one chunk BEFORE its own, the work of the
+//     passes before it: its table has a leading empty entry, its claim counter starts at n_tiles and
+//     its flags at 1, so its units are chunks 1.. and its first chunk takes the stored sums
+//     (`if (k)`) with its flag already set.  A new image (b == 0) starts at chunk 0 from 0.
+// n_units = n_tiles x (the chunks up to the pass's last), so nothing claims the chunk after.
+// Direct mode numbers its items from 0 (they index samples[]); path_loop adds KernelParams::s_begin
+// to the sample that keys the stream, and accum_reduce_kernel adds the stored colors to the sums.
+struct AccumReduceArgs {
+    const double* samples;     // [n][P][3] the pass's stored colors
+    double* sums;              // [P][3] the caller's accumulator (unscaled)
+    uint32_t P, n;
+    uint32_t load;             // 1: continue from sums[q]; 0: a new image, start from 0
+};
 
 // samples [*s0, *s0 + *n) of chunk k (the table is read-only: scalar loads)
 __device__ __forceinline__ void chunk_range(const UnitArgs& u, uint32_t k, uint32_t* s0, uint32_t* n) {
@@ -147,7 +168,10 @@ struct KernelParams {
     uint64_t seed_mix;  // sm_mix(seed), hoisted from sample_key
     uint32_t row0, row_step, n_rows, n_spheres;
     uint32_t n_pad;  // n_spheres rounded up to kPad (sentinel-padded)
-    uint32_t s_begin, s_count;  // unused by the unit scheduler (kept for the kernarg layout)
+    // the launch renders samples [s_begin, s_begin + s_count) (s_begin > 0: an accumulate pass).
+    // s_count sizes the grid (launch wrappers); s_begin is read by the direct-mode kernels only,
+    // which add it to the item's sample for the stream key (ring mode: absolute chunk table)
+    uint32_t s_begin, s_count;
     uint32_t prof;   // 1: instrumented build, stats holds RT_PROFILE_STATS_WORDS entries (rt.h)
     uint32_t pad2[2];
     FastDiv div_layer;  // / (n_rows * width): item -> (sample, pixel) in the refill
@@ -248,6 +272,16 @@ __host__ __device__ inline uint32_t bvh_leaves_offset(uint32_t n_nodes) {
 // small launch), before the ring's bound — the runtime sizes the ring to it (ua may be null then).
 // Direct mode's second pass: per pixel, the stored colors added in sample order, scaled, written.
 extern "C" hipError_t rtk_launch_reduce(const rtk::UnitArgs* ua, hipStream_t stream);
+// Direct mode's second pass of an accumulate pass: a->sums[q] (+)= the stored colors, unscaled.
+extern "C" hipError_t rtk_launch_accum_reduce(const rtk::AccumReduceArgs* a, hipStream_t stream);
+// Ring mode's chunk table of a CONTINUING accumulate pass, from the launch's own table
+// rel[0..n_chunks] (samples numbered from 0): tab[0] = s_begin, the empty chunk that stands for the
+// passes before, and tab[1 + i] = s_begin + rel[i] (n_chunks + 2 entries).
+extern "C" hipError_t rtk_launch_accum_schedule(const uint32_t* rel, uint32_t* tab, uint32_t n_chunks,
+                                                uint32_t s_begin, hipStream_t stream);
+// out[q] = accum[q] * scale for n_pixels pixels (format 0: linear f64; 1: Color.toRgb bytes).
+extern "C" hipError_t rtk_launch_resolve(const double* accum, uint64_t n_pixels, double scale, uint32_t format,
+                                         void* out, hipStream_t stream);
 extern "C" hipError_t rtk_launch_fold_rest(const rtk::FoldArgs* f, hipStream_t stream);
 extern "C" hipError_t rtk_launch_samples(const rtk::KernelParams* p, const rtk::GeoRec* geo,
                                          const rtk::MatRec* mat, const rtk::UnitArgs* ua,

@@ -23,6 +23,11 @@
 //   (camera.zig:135 `pixelColor += rayColor(ray)`, the same sequence of roundings as the reference's
 //   loop), then scales by pixelSamplesScale (camera.zig:137) and writes linear f64 or the fused
 //   Color.toRgb bytes (color.zig:63-80).
+//
+// Progressive rendering (rt_render_rows_accumulate / rt_accum_resolve, rt_kernel.h "Accumulate
+//   passes"): accum_reduce_kernel (direct mode's reduce pass onto the caller's unscaled sums),
+//   accum_schedule_kernel (ring mode's chunk table of a continuing pass) and resolve_kernel (sums x
+//   1/samples -> linear f64 or Color.toRgb bytes); the ring-mode sample kernels are unchanged.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1427,6 +1432,10 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
         // are free (or the wave has no path left), so seeding / getRay run with fuller waves
         if (kRefillMin == 0 || __popcll(__ballot(!active)) >= kRefillMin || __ballot(active) == 0)
             us.refill(active, fresh, myslot, mi, fq, fs, lane);
+        // fs keys the item's stream.  Direct mode numbers a launch's samples from 0 (the item indexes
+        // samples[]): an accumulate pass's first sample is added here (plain launches: 0); ring
+        // mode's chunk table holds absolute sample numbers (rt_kernel.h "Accumulate passes")
+        if constexpr (kDirect) fs += p.s_begin;
         uint64_t t_ref = 0;
         if constexpr (kProf) {
             if (us.drained && !was_drained) rt_drain = __builtin_amdgcn_s_memrealtime();
@@ -2000,6 +2009,64 @@ __global__ __launch_bounds__(256) void reduce_kernel(UnitArgs ua) {
 
 __global__ __launch_bounds__(256) void fold_rest_kernel(FoldArgs f) { fold_chunks(f, lane_id()); }
 
+// Direct mode's second pass of an accumulate pass (rt_render_rows_accumulate): the same ordered
+// additions as reduce_kernel, started from the pixel's stored sum when the pass continues an image
+// (a.load; a new image starts from 0 and overwrites), and the UNSCALED sum written back to the
+// caller's accumulator a.sums.
+__global__ __launch_bounds__(256) void accum_reduce_kernel(AccumReduceArgs a) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.P) return;
+    double* acc = a.sums + 3 * (size_t)q;
+    const double* src = a.samples + 3 * (size_t)q;
+    const size_t stride = 3 * (size_t)a.P;
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (a.load) {
+        x = acc[0];
+        y = acc[1];
+        z = acc[2];
+    }
+#pragma unroll 8
+    for (uint32_t s = 0; s < a.n; ++s) {
+        x = x + src[0];
+        y = y + src[1];
+        z = z + src[2];
+        src += stride;
+    }
+    acc[0] = x;
+    acc[1] = y;
+    acc[2] = z;
+}
+
+// Ring mode's chunk table of a continuing accumulate pass (rt_kernel.h "Accumulate passes"), written
+// on the launch stream so that passes can be queued without a host wait.
+__global__ __launch_bounds__(256) void accum_schedule_kernel(const uint32_t* __restrict__ rel, uint32_t* __restrict__ tab,
+                                                             uint32_t n_chunks, uint32_t s_begin) {
+    for (uint32_t i = threadIdx.x; i <= n_chunks; i += blockDim.x) tab[1 + i] = s_begin + rel[i];
+    if (threadIdx.x == 0) tab[0] = s_begin;
+}
+
+// rt_accum_resolve: avgColor = pixelColor * pixelSamplesScale (camera.zig:137) of an accumulator,
+// thread q one pixel; linear f64 or the fused Color.toRgb bytes.  HBM-bound (24 B in, 24 or 3 B out).
+template <int kOut>
+__global__ __launch_bounds__(256) void resolve_kernel(const double* __restrict__ accum, uint64_t n_pixels, double scale,
+                                                      void* __restrict__ out) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pixels) return;
+    const double* a = accum + 3 * q;
+    const double x = a[0] * scale, y = a[1] * scale, z = a[2] * scale;
+    if constexpr (kOut == 0) {
+        double* o = (double*)out + 3 * q;
+        o[0] = x;
+        o[1] = y;
+        o[2] = z;
+    } else {
+        uint8_t* o = (uint8_t*)out + 3 * q;
+        o[0] = to_byte(x);
+        o[1] = to_byte(y);
+        o[2] = to_byte(z);
+    }
+}
+
 }  // namespace rtk
 
 // ------------------------------------------------------------------------------------------------
@@ -2215,5 +2282,33 @@ extern "C" hipError_t rtk_launch_reduce(const rtk::UnitArgs* ua, hipStream_t str
         hipLaunchKernelGGL(reduce_kernel<0>, dim3(blocks), dim3(256), 0, stream, *ua);
     else
         hipLaunchKernelGGL(reduce_kernel<1>, dim3(blocks), dim3(256), 0, stream, *ua);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_accum_reduce(const rtk::AccumReduceArgs* a, hipStream_t stream) {
+    using namespace rtk;
+    if (a->P == 0 || a->samples == nullptr || a->sums == nullptr) return hipErrorInvalidValue;
+    const uint32_t blocks = (a->P + 255) / 256;
+    hipLaunchKernelGGL(accum_reduce_kernel, dim3(blocks), dim3(256), 0, stream, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_accum_schedule(const uint32_t* rel, uint32_t* tab, uint32_t n_chunks,
+                                                uint32_t s_begin, hipStream_t stream) {
+    using namespace rtk;
+    if (rel == nullptr || tab == nullptr || n_chunks == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(accum_schedule_kernel, dim3(1), dim3(256), 0, stream, rel, tab, n_chunks, s_begin);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_resolve(const double* accum, uint64_t n_pixels, double scale, uint32_t format,
+                                         void* out, hipStream_t stream) {
+    using namespace rtk;
+    if (accum == nullptr || out == nullptr || n_pixels == 0 || n_pixels >= (1ull << 32)) return hipErrorInvalidValue;
+    const uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
+    if (format == 0)
+        hipLaunchKernelGGL(resolve_kernel<0>, dim3(blocks), dim3(256), 0, stream, accum, n_pixels, scale, out);
+    else
+        hipLaunchKernelGGL(resolve_kernel<1>, dim3(blocks), dim3(256), 0, stream, accum, n_pixels, scale, out);
     return hipGetLastError();
 }

@@ -152,6 +152,8 @@ struct rt_context {
     std::vector<uint32_t> sched;    // chunk table of the last launch (rt_schedule.hpp), and its copy
     uint32_t* d_sched = nullptr;
     size_t sched_bytes = 0;
+    uint32_t* d_sched_acc = nullptr;  // the table of a continuing accumulate pass (absolute samples, rt_kernel.h)
+    size_t sched_acc_bytes = 0;
     uint64_t sched_lanes = 0;       // resident lanes the schedule is sized for (CUs x 16 waves x 64)
     unsigned long long* d_ctr = nullptr;  // rtk::kCtrBytes, zeroed per launch ([kErrWord]: error word)
     const char* last_kernel = "sample_kernel";
@@ -765,7 +767,7 @@ int rt_context_destroy(rt_context* ctx) {
         (void)hipDeviceSynchronize();
     }
     for (void* p : {(void*)ctx->d_geo, (void*)ctx->d_mat, (void*)ctx->d_ring, (void*)ctx->d_sums, (void*)ctx->d_flags,
-                    (void*)ctx->d_samples, (void*)ctx->d_samples2, (void*)ctx->d_fold_ctr, (void*)ctx->d_sched, (void*)ctx->d_ctr, (void*)ctx->d_nodes, (void*)ctx->d_leaves, (void*)ctx->d_always_geo,
+                    (void*)ctx->d_samples, (void*)ctx->d_samples2, (void*)ctx->d_fold_ctr, (void*)ctx->d_sched, (void*)ctx->d_sched_acc, (void*)ctx->d_ctr, (void*)ctx->d_nodes, (void*)ctx->d_leaves, (void*)ctx->d_always_geo,
                     (void*)ctx->d_always_sid, ctx->d_out, (void*)ctx->d_stats})
         (void)hipFree(p);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
@@ -816,9 +818,12 @@ namespace {
 // completed in os's order (os may be the null stream): direct mode's reduce pass runs on os after the sample kernel on s, over
 // one of two per-sample buffers taken in turn, so the next call's sample kernel on s need not wait
 // for this call's reduce pass (rt_render_rows_async_split).
+// accum_begin >= 0: an accumulate pass (rt_render_rows_accumulate) — cam->samples_per_pixel is the
+// pass's sample count, its first sample is accum_begin, d_out is the caller's accumulator of unscaled
+// sums, which the sample kernel (ring mode) or the reduce pass (direct mode) adds to.
 int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, uint32_t row0, uint32_t row_step,
                 uint32_t n_rows, void* d_out, void* d_stats, hipStream_t s, hipStream_t os, bool split,
-                bool defer) {
+                bool defer, int64_t accum_begin = -1) {
     if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
     int rc = validate_camera(cam);
     if (rc) return rc;
@@ -866,6 +871,13 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
     trace_mark("schedule_upload");
     ua.chunk_s0 = ctx->d_sched;
     ua.n_chunks = (uint32_t)(ctx->sched.size() - 1);
+    // Accumulate passes (rt_kernel.h): a pass that continues an image counts the passes before it as
+    // chunk 0 — its own chunks are 1.., over a table with a leading empty entry — so that its first
+    // chunk takes the stored sums; a new image starts at chunk 0 from 0, like a plain launch
+    const bool accum = accum_begin >= 0;
+    const uint32_t lead = accum && accum_begin > 0 ? 1u : 0u;
+    const uint32_t table_chunks = ua.n_chunks;
+    ua.n_chunks += lead;
     if (n_tiles * ua.n_chunks >= (1ull << 32)) {
         rt_set_last_error("too many work units (rows x samples): render fewer rows per call");
         return RT_ERR_CAPACITY;
@@ -887,7 +899,7 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
     const bool bvh = use_bvh(ctx);
     rtk::KernelParams p = make_params(cam, row0, row_step, n_rows, ctx->n_spheres);
     p.prof = ctx->profile && d_stats ? 1u : 0u;
-    p.s_begin = 0;
+    p.s_begin = accum ? (uint32_t)accum_begin : 0u;  // the stream keys' first sample (rt_kernel.h)
     p.s_count = cam->samples_per_pixel;
     // the launch for this call's kernel (plan_waves != nullptr: size the grid, launch nothing)
     auto launch = [&](const rtk::UnitArgs* u, uint32_t* plan_waves) -> hipError_t {
@@ -939,10 +951,13 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
         ctx->samples_flip = 0;
         if (!rc) rc = fit_buffer(ctx, (void**)&ctx->d_ring, &ctx->ring_bytes, (size_t)waves * kWaveBytes);
         ctx->ring_waves = rc ? 0u : (uint32_t)(ctx->ring_bytes / kWaveBytes);
-        if (!rc && ua.n_chunks > 1) rc = fit_buffer(ctx, (void**)&ctx->d_sums, &ctx->sums_bytes, P * 3 * sizeof(double));
+        // (an accumulate pass keeps its running sums in the caller's accumulator)
+        if (!rc && ua.n_chunks > 1 && !accum) rc = fit_buffer(ctx, (void**)&ctx->d_sums, &ctx->sums_bytes, P * 3 * sizeof(double));
     }
     const size_t flag_bytes = (n_tiles * sizeof(uint32_t) + 15) & ~(size_t)15;  // memset in 16-B multiples
     if (!rc) rc = ensure_buffer(ctx, (void**)&ctx->d_flags, &ctx->flags_bytes, flag_bytes);
+    if (!rc && lead && !direct)
+        rc = ensure_buffer(ctx, (void**)&ctx->d_sched_acc, &ctx->sched_acc_bytes, (table_chunks + 2) * sizeof(uint32_t));
     if (!rc && defer_fold && !ctx->d_fold_ctr) {
         size_t fb = 0;
         rc = ensure_buffer(ctx, (void**)&ctx->d_fold_ctr, &fb, 2 * 16 * sizeof(unsigned long long));
@@ -958,7 +973,8 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
     if (rc) return rc;
     trace_mark("workspace_alloc");
     ua.ring = direct ? nullptr : ctx->d_ring;
-    ua.sums = direct ? nullptr : ctx->d_sums;
+    ua.sums = accum ? (double*)d_out : (direct ? nullptr : ctx->d_sums);
+    if (lead && !direct) ua.chunk_s0 = ctx->d_sched_acc;
     ua.samples = direct ? (sbuf ? ctx->d_samples2 : ctx->d_samples) : nullptr;
     ua.spp = cam->samples_per_pixel;
     ua.flags = ctx->d_flags;
@@ -966,6 +982,9 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
     ua.ctr = ctx->d_ctr;
     ua.n_tiles = (uint32_t)n_tiles;
     ua.n_units = direct ? (uint32_t)(P * cam->samples_per_pixel) : (uint32_t)(n_tiles * ua.n_chunks);
+    // an accumulate pass: the next pass is the accumulation's next chunk, so the pass's last chunk
+    // stores its sums like the others (rt_kernel.h); n_units above counts the chunks up to that one
+    if (accum) ua.n_chunks += 1;
     ua.div_p = rtk::fastdiv_make((uint32_t)P);
     ua.div_tiles = rtk::fastdiv_make((uint32_t)n_tiles);
     ua.P = (uint32_t)P;
@@ -1003,7 +1022,17 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
         HIP_CHECK(hipMemsetAsync(ctx->fold.ctr, 0, sizeof(unsigned long long), s));
     }
     HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrLaunchBytes, s));  // not the sticky error word
-    if (!direct) HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, flag_bytes, s));
+    if (!direct && lead) {
+        // a continuing accumulate pass in ring mode: chunk 0 is behind it — the claim counter starts
+        // at chunk 1's first unit (the low word of the 64-bit counter; n_tiles < 2^32), every tile's
+        // flag says "chunk 0 finalised", and the table is the launch's own shifted by one entry and
+        // by the pass's first sample.  All on the launch stream: queued passes need no host wait.
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ctx->d_ctr, (int)(uint32_t)n_tiles, 1, s));
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)ctx->d_flags, 1, flag_bytes / sizeof(uint32_t), s));
+        HIP_CHECK(rtk_launch_accum_schedule(ctx->d_sched, ctx->d_sched_acc, table_chunks, p.s_begin, s));
+    } else if (!direct) {
+        HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, flag_bytes, s));
+    }
     hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
     if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
     trace_mark("launch_setup");
@@ -1049,7 +1078,12 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
         ctx->fold_stream = rs;
         ctx->fold_pending = true;
     } else if (direct) {
-        HIP_CHECK(rtk_launch_reduce(&ua, rs));
+        if (accum) {
+            rtk::AccumReduceArgs ra{ua.samples, (double*)d_out, ua.P, ua.spp, accum_begin > 0 ? 1u : 0u};
+            HIP_CHECK(rtk_launch_accum_reduce(&ra, rs));
+        } else {
+            HIP_CHECK(rtk_launch_reduce(&ua, rs));
+        }
         HIP_CHECK(hipEventRecord(ctx->reduced[sbuf], rs));
         ctx->reduced_valid[sbuf] = true;
     }
@@ -1086,6 +1120,42 @@ int rt_render_rows_async_deferred(rt_context* ctx, const rt_camera* cam, uint32_
     }
     return render_rows(ctx, cam, output_format, row0, row_step, n_rows, d_out, d_stats, (hipStream_t)stream,
                        (hipStream_t)out_stream, true, true);
+}
+
+int rt_render_rows_accumulate(rt_context* ctx, const rt_camera* cam, uint32_t row0, uint32_t row_step, uint32_t n_rows,
+                              uint32_t sample_begin, uint32_t sample_count, void* d_accum, void* d_stats,
+                              void* stream) {
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (!cam) { rt_set_last_error("null camera"); return RT_ERR_INVALID; }
+    if (!d_accum) { rt_set_last_error("null accumulator"); return RT_ERR_INVALID; }
+    if (sample_count == 0 || n_rows == 0) return RT_OK;
+    if ((uint64_t)sample_begin + sample_count > 0xffffffffull) {
+        rt_set_last_error("sample_begin + sample_count exceeds 2^32 - 1");
+        return RT_ERR_INVALID;
+    }
+    // the pass is a plain one-stream launch of its own samples: the camera's sample count (unused by
+    // the contract) becomes the pass's, which sizes the schedule, the unit mode and the BVH training;
+    // nothing is scaled (rt_accum_resolve does that)
+    rt_camera c = *cam;
+    c.samples_per_pixel = sample_count;
+    c.pixel_samples_scale = 1.0;
+    return render_rows(ctx, &c, RT_OUT_LINEAR_F64, row0, row_step, n_rows, d_accum, d_stats, (hipStream_t)stream,
+                       nullptr, false, false, (int64_t)sample_begin);
+}
+
+int rt_accum_resolve(rt_context* ctx, const void* d_accum, uint64_t n_pixels, uint32_t n_samples,
+                     uint32_t output_format, void* d_out, void* stream) {
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (!d_accum || !d_out) { rt_set_last_error("null accumulator / output"); return RT_ERR_INVALID; }
+    if (output_format > RT_OUT_RGB8) { rt_set_last_error("bad output_format"); return RT_ERR_INVALID; }
+    if (n_samples == 0) { rt_set_last_error("n_samples must be > 0"); return RT_ERR_INVALID; }
+    if (n_pixels >= (1ull << 32)) { rt_set_last_error("n_pixels must be below 2^32"); return RT_ERR_INVALID; }
+    if (n_pixels == 0) return RT_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    // Camera.pixelSamplesScale (camera.zig:284): 1.0 / spp, one correctly rounded division
+    const double scale = 1.0 / (double)n_samples;
+    HIP_CHECK(rtk_launch_resolve((const double*)d_accum, n_pixels, scale, output_format, d_out, (hipStream_t)stream));
+    return RT_OK;
 }
 
 int rt_context_fold_pending(rt_context* ctx, int* pending) {
@@ -1174,7 +1244,7 @@ int rt_context_tree_info(rt_context* ctx, uint32_t* info) {
 int rt_context_workspace_bytes(rt_context* ctx, uint64_t* bytes) {
     if (!ctx || !bytes) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
     *bytes = (uint64_t)ctx->ring_bytes + ctx->sums_bytes + ctx->flags_bytes + ctx->samples_bytes + ctx->samples2_bytes +
-             ctx->sched_bytes + (ctx->d_fold_ctr ? 2 * 16 * sizeof(unsigned long long) : 0) +
+             ctx->sched_bytes + ctx->sched_acc_bytes + (ctx->d_fold_ctr ? 2 * 16 * sizeof(unsigned long long) : 0) +
              (ctx->d_ctr ? rtk::kCtrBytes : 0);
     return RT_OK;
 }

@@ -147,6 +147,13 @@ class Camera:
                    render(self.cam, self.scene.world, n_gpus=n_gpus, device=device,
                           output=output, stats=stats, precision=precision))
 
+    def render_progressive(self, passes, device=0, output="linear", precision="f64"):
+        """Generator over (samples_done, PPM) after each pass of `passes` samples (render_progressive);
+        samplesPerPixel of the camera is not used."""
+        for done, img in render_progressive(self.cam, self.scene.world, passes, device=device, output=output,
+                                            precision=precision):
+            yield done, PPM(self.width, self.height, img)
+
 
 _PRECISION = {"f64": abi.RT_PRECISION_F64, "f32": abi.RT_PRECISION_F32}
 
@@ -175,6 +182,45 @@ def render(cam, spheres, n_gpus=0, device=0, output="linear", stats=None, precis
         stats["rays"] = st[0]
         stats["samples"] = st[1]
     return out
+
+
+def render_progressive(cam, spheres, passes, device=0, output="linear", precision="f64"):
+    """Progressive render on one GPU: a generator that renders `passes` (a sequence of sample counts)
+    one after the other onto one device accumulator and yields (samples_done, image) after each —
+    the image a one-pass render at spp = samples_done gives, bit for bit (linear -> (H, W, 3) f64,
+    rgb8 -> (H, W, 3) u8).  cam.samples_per_pixel is not used.  Stopping the generator early stops
+    the render; the device buffers are torch tensors (imported here, not with the package)."""
+    if output not in ("linear", "rgb8"):
+        raise ValueError(output)
+    passes = [int(n) for n in passes]
+    if any(n < 0 for n in passes):
+        raise ValueError("passes must be sample counts >= 0")
+    import torch
+
+    W, H = cam.image_width, cam.image_height
+    n = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * n)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        r.set_precision(precision)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            accum = torch.empty((H * W, 3), dtype=torch.float64, device=dev)
+            out = torch.empty((H, W, 3), dtype=torch.float64 if output == "linear" else torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            done = 0
+            for count in passes:
+                r.accumulate(cam, accum.data_ptr(), done, count, stream_ptr=stream)
+                done += count
+                if done == 0:
+                    continue  # nothing accumulated yet: no image to show
+                r.resolve(accum.data_ptr(), H * W, done, out.data_ptr(), output=output, stream_ptr=stream)
+                img = out.cpu().numpy()  # waits for the stream
+                r.sync()  # reports a failure the kernel recorded
+                yield done, img
+    finally:
+        r.close()
 
 
 class DeviceRenderer:
@@ -217,6 +263,27 @@ class DeviceRenderer:
               self.lib.rt_render_rows_async(self.ctx, C.byref(cam), fmt, row0, row_step, n_rows,
                                             C.c_void_p(d_out_ptr), C.c_void_p(d_stats_ptr or 0),
                                             C.c_void_p(stream_ptr or 0)))
+
+    def accumulate(self, cam, d_accum_ptr, sample_begin, sample_count, row0=0, row_step=1, n_rows=None,
+                   d_stats_ptr=None, stream_ptr=None):
+        """rt_render_rows_accumulate: samples [sample_begin, sample_begin + sample_count) added, in
+        sample order, to the unscaled per-pixel sums at d_accum_ptr (n_rows * W x 3 f64 on the device).
+        sample_begin == 0 starts a new image (the buffer need not be initialised); any split of
+        [0, n) into consecutive passes resolves to the bits of a one-pass render at n samples."""
+        if n_rows is None:
+            n_rows = (cam.image_height - row0 + row_step - 1) // row_step
+        check("rt_render_rows_accumulate",
+              self.lib.rt_render_rows_accumulate(self.ctx, C.byref(cam), row0, row_step, n_rows, sample_begin,
+                                                 sample_count, C.c_void_p(d_accum_ptr or 0),
+                                                 C.c_void_p(d_stats_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def resolve(self, d_accum_ptr, n_pixels, n_samples, d_out_ptr, output="linear", stream_ptr=None):
+        """rt_accum_resolve: d_out = d_accum * (1 / n_samples), linear f64 or Color.toRgb bytes; the
+        accumulator is left as it is (a preview; accumulation can go on)."""
+        fmt = abi.RT_OUT_LINEAR_F64 if output == "linear" else abi.RT_OUT_RGB8
+        check("rt_accum_resolve",
+              self.lib.rt_accum_resolve(self.ctx, C.c_void_p(d_accum_ptr or 0), n_pixels, n_samples, fmt,
+                                        C.c_void_p(d_out_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
     def flush(self):
         """Runs a pending deferred reduce pass (rt_context_flush)."""

@@ -20,6 +20,8 @@ EXPORTED = [
     "rt_render_rows_async",
     "rt_render_rows_async_split",
     "rt_render_rows_async_deferred",
+    "rt_render_rows_accumulate",
+    "rt_accum_resolve",
     "rt_context_flush",
     "rt_context_fold_pending",
     "rt_kernel_name",
@@ -71,6 +73,9 @@ def _declare(lib):
                                                  C.c_uint32, vp, vp, vp, vp]),
         "rt_render_rows_async_deferred": (C.c_int, [vp, P(RtCamera), C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_uint32, vp, vp, vp, vp]),
+        "rt_render_rows_accumulate": (C.c_int, [vp, P(RtCamera), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "rt_accum_resolve": (C.c_int, [vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp]),
         "rt_context_flush": (C.c_int, [vp]),
         "rt_context_fold_pending": (C.c_int, [vp, P(C.c_int)]),
         "rt_kernel_name": (C.c_char_p, [vp]),
