@@ -219,6 +219,60 @@ int rt_render_rows_accumulate(rt_context* ctx, const rt_camera* cam,
  * n_pixels >= 2^32. */
 int rt_accum_resolve(rt_context* ctx, const void* d_accum, uint64_t n_pixels, uint32_t n_samples,
                      uint32_t output_format, void* d_out, void* stream);
+/* ---- adaptive sampling: samples added to chosen pixels, bit-exactly -----------
+ * A gather pass.  d_pixels: n_pixels image-global pixel indices j*W + i in DEVICE memory, in any
+ * order, each < W*H and pairwise distinct (a caller contract, like the validity of a pointer); NULL
+ * means every pixel, and then n_pixels must be W*H.  d_accum: [W*H][3] f64 unscaled sums, the buffer
+ * (meaning and bits) of rt_render_rows_accumulate for the whole image.  d_counts: [W*H] u32 samples
+ * done per pixel; the caller zeroes it for a new image.  d_m2: [W*H] f64, may be NULL: the per-pixel
+ * sum of squared sample luminance.
+ * Per listed pixel p, with b = counts[p]: samples [b, b + sample_count) are rendered with their usual
+ * stream keys and their colours added, in sample order, to accum[p]; if d_m2 is given, y*y with
+ * y = (r + g) + b is added to m2[p] in the same order (no weights, no fused multiply-add); then
+ * counts[p] = b + sample_count.  A pixel with b == 0 starts from 0: its accum and m2 entries are
+ * overwritten, not read, and need not be initialised.  Pixels not listed are not touched in any buffer.
+ * So after any sequence of passes every pixel's sums are those of a one-pass render at that pixel's
+ * own count: rt_accum_resolve_counts gives, per pixel, the bits of rt_render_rows_async at
+ * samples_per_pixel = counts[p] (RT_PRECISION_F32 contexts: of the one-pass fast render).  An
+ * accumulator that row passes brought to n samples continues here once counts is filled with n.
+ *
+ * Asynchronous on `stream`; d_stats (2 x uint64) as elsewhere.  A plain one-stream call: a pending
+ * deferred reduce pass runs first.  Always direct mode: the pass's sample buffer is
+ * n_pixels x sample_count x 24 B, and a pass above the 2-GiB cap (RTZIG_GATHER_BYTES, read per call,
+ * lowers it) is split by the library into consecutive sub-passes over the same list; counts carries
+ * the position between them.  The buffer is not given back when a later pass needs less (an adaptive
+ * loop's lists shrink; the next row render applies the workspace rule).  BVH training and tree choice follow n_pixels x sample_count; timing
+ * (rt_context_kernel_times*) covers every sub-pass.  cam->samples_per_pixel and pixel_samples_scale
+ * are unused.  sample_count == 0 or n_pixels == 0: RT_OK, nothing is touched.
+ * RT_ERR_INVALID: null ctx, cam, d_accum or d_counts; a NULL list with n_pixels != W*H;
+ * n_pixels > W*H; an instrumented context (rt_context_enable_profile: gather passes have no
+ * instrumented kernel).  RT_ERR_CAPACITY: one sample of the list alone does not fit the buffer. */
+int rt_render_pixels_accumulate(rt_context* ctx, const rt_camera* cam,
+                                const uint32_t* d_pixels, uint32_t n_pixels,
+                                uint32_t sample_count,
+                                void* d_accum, void* d_m2, uint32_t* d_counts,
+                                void* d_stats, void* stream);
+/* The noise estimate and the ordered selection.  Per pixel, in f64, in exactly this order:
+ *   n = (double)counts[p];  S = (a0 + a1) + a2;  mean = S / n;  v = m2 - S * mean;
+ *   v = v < 0 ? 0 : v;  sem = sqrt((v / (n - 1)) / n);  err = sem / (mean > floor ? mean : floor)
+ * A pixel is selected when counts < min_count, or when counts < max_count && !(err <= tolerance)
+ * (a NaN error keeps sampling until max_count).  The selected indices go to d_list (capacity
+ * n_pixels) in ASCENDING order and their number to *d_n; entries of d_list past *d_n are
+ * unspecified.  d_err (may be NULL) receives err for every pixel, 0 where counts < 2.
+ * Asynchronous on `stream`; three small launches, none waiting on another block.  n_pixels == 0:
+ * *d_n = 0.
+ * RT_ERR_INVALID: null ctx, d_accum, d_m2, d_counts, d_list or d_n; min_count < 2;
+ * max_count < min_count; n_pixels >= 2^32; floor not > 0; tolerance NaN. */
+int rt_accum_select(rt_context* ctx, const void* d_accum, const void* d_m2,
+                    const uint32_t* d_counts, uint64_t n_pixels,
+                    uint32_t min_count, uint32_t max_count,
+                    double tolerance, double floor,
+                    uint32_t* d_list, uint32_t* d_n, double* d_err, void* stream);
+/* d_out[p] = d_accum[p] * (1.0 / (double)counts[p]) (camera.zig:284,137), 0 for a pixel with
+ * counts[p] == 0; linear f64 or the fused Color.toRgb.  Errors as rt_accum_resolve (and null
+ * d_counts). */
+int rt_accum_resolve_counts(rt_context* ctx, const void* d_accum, const uint32_t* d_counts,
+                            uint64_t n_pixels, uint32_t output_format, void* d_out, void* stream);
 /* Runs a pending deferred reduce pass (on the out_stream of the call that deferred it); no-op otherwise. */
 int rt_context_flush(rt_context* ctx);
 /* *pending = 1 if the last deferred call left its output pending (direct mode), else 0. */
@@ -238,7 +292,8 @@ const char* rt_kernel_name(rt_context* ctx);
  * same bits as any tree, fewer node visits)}. */
 int rt_context_tree_info(rt_context* ctx, uint32_t* info);
 /* Device bytes the context's render workspace holds now (rings, sums, flags, direct-mode samples,
- * schedule, counters; not the scene or caller buffers): see rt_render "Workspace". */
+ * schedule, counters, rt_accum_select's scratch; not the scene or caller buffers): see rt_render
+ * "Workspace". */
 int rt_context_workspace_bytes(rt_context* ctx, uint64_t* bytes);
 /* Optional kernel timing with HIP events recorded on the launch stream around the kernels of every
  * render call.  rt_context_kernel_times waits for the last event and returns the durations (ms) of

@@ -121,6 +121,53 @@ struct AccumReduceArgs {
     uint32_t load;             // 1: continue from sums[q]; 0: a new image, start from 0
 };
 
+// Gather passes (rt_render_pixels_accumulate): direct mode over a LIST of L pixels,
+// each at its own sample number.  The items are t = s * L + q (q < L a list entry, s < n the pass's
+// local sample; UnitArgs::P = L, div_p = / L, n_units = L * n, samples[t]); a fresh lane maps q to
+// the image pixel pixels[q] (nullptr: q itself), takes (row, column) from it with div_width and keys
+// its stream with sample counts[pixel] + s.  row0 / row_step / s_begin play no part.  The gather
+// kernels (gather_kernel*, rt_kernel.hip) are path_loop's kGather instantiations: they take these two
+// pointers as a LAST kernel argument, so the kernarg offsets the shared code reads stay put.
+struct GatherArgs {
+    const uint32_t* pixels;    // [L] image-global pixel indices j * W + i, pairwise distinct; nullptr: identity
+    const uint32_t* counts;    // [W * H] samples done per pixel (gather_reduce_kernel advances it)
+};
+// The gather reduce pass: thread q adds the pass's n stored colors of list entry q, in sample order,
+// to sums[pixel] (from 0 when counts[pixel] == 0), their squared luminances to m2[pixel] (optional),
+// and sets counts[pixel] += n last.
+struct GatherReduceArgs {
+    const double* samples;     // [n][L][3]
+    const uint32_t* pixels;    // [L] or nullptr (identity)
+    double* sums;              // [W * H][3] unscaled
+    double* m2;                // [W * H] or nullptr
+    uint32_t* counts;          // [W * H]
+    uint32_t L, n;
+};
+// rt_accum_select: an ordered stream compaction in three launches, none of which
+// waits on another block.  Blocks of kSelBlock threads, one pixel each.  Scratch (the context's):
+// [blocks] u32 block counts (the scan turns them into exclusive offsets in place), then, 8-B aligned,
+// [waves] u64 ballots of the selected pixels.
+constexpr uint32_t kSelBlock = 1024;
+struct SelectArgs {
+    const double* accum;       // [n][3]
+    const double* m2;          // [n]
+    const uint32_t* counts;    // [n]
+    uint32_t n, min_count, max_count, n_blocks;
+    double tolerance, floor;
+    uint32_t* block_counts;    // [n_blocks]
+    unsigned long long* masks; // [ceil(n / 64)]
+    uint32_t* list;            // [n] selected indices, ascending
+    uint32_t* n_out;           // their number
+    double* err;               // [n] or nullptr
+};
+__host__ __device__ inline size_t select_masks_offset(uint32_t n_blocks) {
+    return ((size_t)n_blocks * sizeof(uint32_t) + 7) & ~(size_t)7;
+}
+__host__ __device__ inline size_t select_scratch_bytes(uint64_t n) {
+    const uint32_t nb = (uint32_t)((n + kSelBlock - 1) / kSelBlock);
+    return select_masks_offset(nb) + (size_t)((n + 63) / 64) * sizeof(unsigned long long);
+}
+
 // samples [*s0, *s0 + *n) of chunk k (the table is read-only: scalar loads)
 __device__ __forceinline__ void chunk_range(const UnitArgs& u, uint32_t k, uint32_t* s0, uint32_t* n) {
     const uint32_t a = u.chunk_s0[k], b = u.chunk_s0[k + 1];
@@ -297,5 +344,17 @@ extern "C" hipError_t rtk_launch_samples_fast(const rtk::KernelParams* p, const 
                                               const rtk::MatRec* mat, const rtk::UnitArgs* ua, void* stats,
                                               hipStream_t stream, const char** name, bool direct,
                                               uint32_t* plan_waves);
+// Gather passes (rtk::GatherArgs): the direct-mode gather twin of the kernel the context would launch
+// — `b` == nullptr: the list walk; else the BVH walk, in f32 when `fast` — over ua's L x n items
+// (ua->P = L, ua->spp = n, ua->n_units = L * n, ua->samples).  No instrumented form.
+extern "C" hipError_t rtk_launch_gather(const rtk::KernelParams* p, const rtk::BvhArgs* b, bool fast,
+                                        const rtk::GeoRec* geo, const rtk::MatRec* mat, const rtk::UnitArgs* ua,
+                                        const rtk::GatherArgs* ga, void* stats, hipStream_t stream, const char** name);
+extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, hipStream_t stream);
+// rt_accum_select's three launches (count, scan, scatter) over a->n pixels.
+extern "C" hipError_t rtk_launch_select(const rtk::SelectArgs* a, hipStream_t stream);
+// out[q] = accum[q] * (1.0 / counts[q]) (0 where counts[q] == 0), formats as rtk_launch_resolve.
+extern "C" hipError_t rtk_launch_resolve_counts(const double* accum, const uint32_t* counts, uint64_t n_pixels,
+                                                uint32_t format, void* out, hipStream_t stream);
 // Resident blocks of `kernel` on the current device (CUs x occupancy), cached (rt_kernel.hip).
 extern "C" hipError_t rtk_resident_blocks(const void* kernel, int block, size_t shmem, uint32_t* blocks);

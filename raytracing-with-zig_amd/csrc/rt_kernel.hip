@@ -28,6 +28,14 @@
 //   passes"): accum_reduce_kernel (direct mode's reduce pass onto the caller's unscaled sums),
 //   accum_schedule_kernel (ring mode's chunk table of a continuing pass) and resolve_kernel (sums x
 //   1/samples -> linear f64 or Color.toRgb bytes); the ring-mode sample kernels are unchanged.
+//
+// Adaptive sampling (rt_render_pixels_accumulate / rt_accum_select / rt_accum_resolve_counts,
+//   rt_kernel.h "Gather passes"): gather_kernel, gather_kernel_bvh and gather_kernel_fast are
+//   path_loop's kGather instantiations (direct mode over a pixel list, every pixel at its own sample
+//   number), gather_reduce_kernel their reduce pass (sums, squared luminances, counts),
+//   select_count / select_scan / select_scatter_kernel the ordered selection of the pixels that need
+//   more samples, resolve_counts_kernel the resolve with a per-pixel scale.  The existing kernels
+//   compile to the same instructions as before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1340,10 +1348,17 @@ __device__ __forceinline__ void fold_chunks(const FoldArgs& f, uint32_t lane) {
 // ------------------------------------------------------------------------------------------------
 // kWin: fresh lanes take their generator and pixel sample point from the wave's seed window in LDS
 // (`win`: its address; kSeedWin builds of the f64 BVH kernel).
-template <bool kProf, bool kDirect, bool kWin = false, class Walker>
+// kGather: a gather pass (rt_kernel.h GatherArgs; direct mode only) — an item's launch-local "pixel"
+// is an entry of the list g_pixels, and its sample is local to the pass: a fresh lane (or the seed
+// window, for its 64 list entries) takes the image pixel from the list and adds the pixel's own
+// count g_counts[pixel] to the sample that keys the stream.  Everything else is direct mode.
+template <bool kProf, bool kDirect, bool kWin = false, bool kGather = false, class Walker>
 __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& walk, const GeoRec* __restrict__ geo_orig,
                                           const MatRec* __restrict__ mat_g, const UnitArgs& ua,
-                                          unsigned long long* __restrict__ stats, uint32_t win = 0) {
+                                          unsigned long long* __restrict__ stats, uint32_t win = 0,
+                                          const uint32_t* __restrict__ g_pixels = nullptr,
+                                          const uint32_t* __restrict__ g_counts = nullptr) {
+    static_assert(!kGather || (kDirect && !kProf), "gather passes: direct mode, no instrumented form");
     const uint32_t W = p.width;
     const uint32_t lane = lane_id();
     UnitSched<kDirect> us(ua, blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64);
@@ -1402,7 +1417,7 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
     // by the first kFoldHead waves of every block before they trace, while the block's other waves
     // trace; the drained waves at the end take what is left (below).  Left to the drained waves
     // alone, most of it waited for waves to finish their last long paths and ran after the tail.
-    if constexpr (kDirect && !kProf) {
+    if constexpr (kDirect && !kProf && !kGather) {
         if (kFoldHead > 0 && ua.fold.samples != nullptr && threadIdx.x / 64 < (uint32_t)kFoldHead) fold_chunks(ua.fold, lane);
     }
 
@@ -1435,7 +1450,8 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
         // fs keys the item's stream.  Direct mode numbers a launch's samples from 0 (the item indexes
         // samples[]): an accumulate pass's first sample is added here (plain launches: 0); ring
         // mode's chunk table holds absolute sample numbers (rt_kernel.h "Accumulate passes")
-        if constexpr (kDirect) fs += p.s_begin;
+        // (a gather pass adds each pixel's own count where the stream is keyed, below)
+        if constexpr (kDirect && !kGather) fs += p.s_begin;
         uint64_t t_ref = 0;
         if constexpr (kProf) {
             if (us.drained && !was_drained) rt_drain = __builtin_amdgcn_s_memrealtime();
@@ -1472,12 +1488,20 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
                         wkey[0] = kt;
                         wkey[1] = ks;
                     }
-                    const uint32_t q = kt * 64 + lane;  // past the launch's last pixel: computed, never read
+                    uint32_t q = kt * 64 + lane;  // past the launch's last pixel: computed, never read
+                    uint32_t ksl = ks;            // the sample this lane's entry is keyed with
+                    if constexpr (kGather) {
+                        // list entries past the last are computed from a clamped index, never read;
+                        // each lane seeds its own listed pixel at that pixel's own absolute sample
+                        q = q < ua.P ? q : ua.P - 1;
+                        if (g_pixels) q = g_pixels[q];
+                        ksl += g_counts[q];
+                    }
                     const uint32_t row_local = fastdiv(q, p.div_width);
                     const uint32_t i = q - row_local * W;
-                    const uint32_t j = p.row0 + row_local * p.row_step;
+                    const uint32_t j = kGather ? row_local : p.row0 + row_local * p.row_step;
                     Rng gw;
-                    gw.seed(sample_key(p.seed_mix, (uint64_t)j * W + i, ks));
+                    gw.seed(sample_key(p.seed_mix, (uint64_t)j * W + i, ksl));
                     uint64_t w[7];
                     if constexpr (kF32) {  // fast mode: camera_start's f32 ray direction (2 planes unused)
                         fm::Ray rw;
@@ -1535,9 +1559,13 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
                 todo &= ~__ballot(mine);
             }
         } else if (fresh) {
+            if constexpr (kGather) {
+                if (g_pixels) fq = g_pixels[fq];
+                fs += g_counts[fq];
+            }
             const uint32_t row_local = fastdiv(fq, p.div_width);
             const uint32_t i = fq - row_local * W;
-            const uint32_t j = p.row0 + row_local * p.row_step;
+            const uint32_t j = kGather ? row_local : p.row0 + row_local * p.row_step;
             const uint64_t pixel = (uint64_t)j * W + i;
             g.seed(sample_key(p.seed_mix, pixel, fs));
             dpend = camera_start(i, j, g, r);
@@ -1812,7 +1840,7 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
 
     // the previous direct-mode call's reduce pass, taken up by the waves that ran out of items while a
     // few long paths finish elsewhere (rt_render_rows_async_deferred; empty otherwise)
-    if constexpr (kDirect && !kProf) {
+    if constexpr (kDirect && !kProf && !kGather) {
         if (ua.fold.samples != nullptr) fold_chunks(ua.fold, lane);
     }
     RTK_MARK("epilogue");
@@ -1924,6 +1952,23 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves))
         (unsigned char*)lds_geo + (kLds ? (size_t)p.n_pad * sizeof(GeoRec) : 0) + (threadIdx.x / 64) * kSeedWinBytes);
     path_loop<kProf, kDirect, kSeedWin>(p, LinearWalker<U>{geo, p.n_pad, p.n_spheres}, geo, mat_g, ua, stats, win);
 }
+// ... and its gather twin (rt_kernel.h GatherArgs): the same body in direct mode over a pixel list.
+template <bool kLds, int U, int kWaves>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves))) void gather_kernel(
+    KernelParams p, const GeoRec* __restrict__ geo_g, const MatRec* __restrict__ mat_g, UnitArgs ua,
+    unsigned long long* __restrict__ stats, GatherArgs ga) {
+    extern __shared__ GeoRec lds_geo[];
+    const GeoRec* geo = geo_g;
+    if constexpr (kLds) {
+        for (uint32_t k = threadIdx.x; k < p.n_pad; k += blockDim.x) lds_geo[k] = geo_g[k];
+        __syncthreads();
+        geo = lds_geo;
+    }
+    const uint32_t win = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(
+        (unsigned char*)lds_geo + (kLds ? (size_t)p.n_pad * sizeof(GeoRec) : 0) + (threadIdx.x / 64) * kSeedWinBytes);
+    path_loop<false, true, kSeedWin, true>(p, LinearWalker<U>{geo, p.n_pad, p.n_spheres}, geo, mat_g, ua, stats, win,
+                                           ga.pixels, ga.counts);
+}
 
 // BVH-walk kernel: nodes + slot geometry + slot ids staged in LDS (kLdsScene) or read from global
 // memory; the per-lane traversal stack always lives in LDS.
@@ -1945,7 +1990,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves))
 #else
 #define RTK_BOUNDS_ARGS
 #endif
-#define RTK_BVH_BODY(kF32) \
+#define RTK_GATHER_ARGS , ga.pixels, ga.counts
+#define RTK_BVH_BODY(kF32, kGather, GATHER_ARGS) \
     /* LDS: [nodes][leaves] (kLdsScene) at address 0, so a node's byte-offset ref IS its LDS */ \
     /* address; then the per-lane stacks [stack_depth][kB]; then the waves' seed windows */ \
     constexpr int kB = bvh_block(kProf); \
@@ -1973,16 +2019,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWaves))
     const uint32_t win = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)( \
         lds_raw + ((scene_bytes + (size_t)b.stack_depth * kB * sizeof(Stack) + 15) & ~(size_t)15) + \
         (threadIdx.x / 64) * kSeedWinBytes); \
-    path_loop<kProf, kDirect, kSeedWin && kLdsScene>(p, Walker{nodes, leaves, b.always_geo, b.always_sid, b.n_always, \
+    path_loop<kProf, kDirect, kSeedWin && kLdsScene, kGather>(p, Walker{nodes, leaves, b.always_geo, b.always_sid, b.n_always, \
                                          stack + threadIdx.x, b.origin_bound, geo_g, p.n_pad RTK_BOUNDS_ARGS}, geo_g, \
-                              mat_g, ua, stats, win);
+                              mat_g, ua, stats, win GATHER_ARGS);
 
 template <bool kLdsScene, bool kProf, bool kDirect>
 __global__ __launch_bounds__(bvh_block(kProf)) RTK_BVH_WAVES void sample_kernel_bvh(KernelParams p, BvhArgs b,
                                                                const GeoRec* __restrict__ geo_g,
                                                                const MatRec* __restrict__ mat_g, UnitArgs ua,
                                                                unsigned long long* __restrict__ stats) {
-    RTK_BVH_BODY(false)
+    RTK_BVH_BODY(false, false, )
 }
 // Fast mode (RT_PRECISION_F32): the same body in f32, under the same wave bound as the parity kernel
 // (4 waves per SIMD; left alone its ring-mode instantiation takes 131 VGPRs, i.e. 3 waves; the
@@ -1991,8 +2037,25 @@ template <bool kLdsScene, bool kProf, bool kDirect>
 __global__ __launch_bounds__(bvh_block(kProf)) RTK_BVH_WAVES void sample_kernel_fast(
     KernelParams p, BvhArgs b, const GeoRec* __restrict__ geo_g, const MatRec* __restrict__ mat_g, UnitArgs ua,
     unsigned long long* __restrict__ stats) {
-    RTK_BVH_BODY(true)
+    RTK_BVH_BODY(true, false, )
 }
+// The gather twins of the two direct-mode kernels above (rt_kernel.h GatherArgs; no instrumented
+// form): the same body, under the same wave bound, with the pixel list as a last argument.
+template <bool kLdsScene>
+__global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) void gather_kernel_bvh(
+    KernelParams p, BvhArgs b, const GeoRec* __restrict__ geo_g, const MatRec* __restrict__ mat_g, UnitArgs ua,
+    unsigned long long* __restrict__ stats, GatherArgs ga) {
+    constexpr bool kProf = false, kDirect = true;
+    RTK_BVH_BODY(false, true, RTK_GATHER_ARGS)
+}
+template <bool kLdsScene>
+__global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) void gather_kernel_fast(
+    KernelParams p, BvhArgs b, const GeoRec* __restrict__ geo_g, const MatRec* __restrict__ mat_g, UnitArgs ua,
+    unsigned long long* __restrict__ stats, GatherArgs ga) {
+    constexpr bool kProf = false, kDirect = true;
+    RTK_BVH_BODY(true, true, RTK_GATHER_ARGS)
+}
+#undef RTK_GATHER_ARGS
 #undef RTK_BVH_BODY
 
 // Direct mode's second pass (rt_kernel.h "Work units"): thread q adds pixel q's stored colors in
@@ -2054,6 +2117,162 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double* __restrict__
     if (q >= n_pixels) return;
     const double* a = accum + 3 * q;
     const double x = a[0] * scale, y = a[1] * scale, z = a[2] * scale;
+    if constexpr (kOut == 0) {
+        double* o = (double*)out + 3 * q;
+        o[0] = x;
+        o[1] = y;
+        o[2] = z;
+    } else {
+        uint8_t* o = (uint8_t*)out + 3 * q;
+        o[0] = to_byte(x);
+        o[1] = to_byte(y);
+        o[2] = to_byte(z);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Adaptive sampling: the gather reduce pass, the noise estimate + ordered selection,
+// and the per-pixel resolve.
+// ------------------------------------------------------------------------------------------------
+// The reduce pass of a gather pass (rt_kernel.h GatherReduceArgs): accum_reduce_kernel's ordered
+// additions for list entry q, onto the sums of ITS pixel, started from them when the pixel has
+// samples already (counts != 0; else from 0, overwriting), plus the squared luminances
+// y = (r + g) + b, m2 += y * y, in the same order (no contraction in this file).  The listed pixels
+// are pairwise distinct, so no two threads touch one pixel; counts is written last.
+__global__ __launch_bounds__(256) void gather_reduce_kernel(GatherReduceArgs a) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= a.L) return;
+    const uint32_t px = a.pixels ? a.pixels[q] : q;
+    const uint32_t b = a.counts[px];
+    double* acc = a.sums + 3 * (size_t)px;
+    const double* src = a.samples + 3 * (size_t)q;
+    const size_t stride = 3 * (size_t)a.L;
+    double x = 0.0, y = 0.0, z = 0.0, m = 0.0;
+    if (b != 0) {
+        x = acc[0];
+        y = acc[1];
+        z = acc[2];
+        if (a.m2) m = a.m2[px];
+    }
+#pragma unroll 8
+    for (uint32_t s = 0; s < a.n; ++s) {
+        const double r = src[0], g = src[1], bl = src[2];
+        x = x + r;
+        y = y + g;
+        z = z + bl;
+        const double lum = (r + g) + bl;
+        m = m + lum * lum;
+        src += stride;
+    }
+    acc[0] = x;
+    acc[1] = y;
+    acc[2] = z;
+    if (a.m2) a.m2[px] = m;
+    a.counts[px] = b + a.n;
+}
+
+// The noise estimate of pixel q and whether it is selected (rt.h rt_accum_select: the operation
+// order is the contract).  c < 2: err = 0, and the pixel is selected (min_count >= 2).
+__device__ __forceinline__ bool select_pixel(const SelectArgs& a, uint32_t q, double* err_out) {
+    const uint32_t c = a.counts[q];
+    double err = 0.0;
+    if (c >= 2) {
+        const double n = (double)c;
+        const double S = (a.accum[3 * (size_t)q] + a.accum[3 * (size_t)q + 1]) + a.accum[3 * (size_t)q + 2];
+        const double mean = S / n;
+        double v = a.m2[q] - S * mean;
+        v = v < 0 ? 0 : v;
+        const double sem = __builtin_sqrt((v / (n - 1)) / n);
+        err = sem / (mean > a.floor ? mean : a.floor);
+    }
+    *err_out = err;
+    return c < a.min_count || (c < a.max_count && !(err <= a.tolerance));
+}
+// Pass 1: every wave's ballot of its selected pixels -> masks[wave]; their number per block ->
+// block_counts[block]; err[] if asked for.
+__global__ __launch_bounds__(kSelBlock) void select_count_kernel(SelectArgs a) {
+    __shared__ uint32_t wc[kSelBlock / 64];
+    const uint32_t q = blockIdx.x * kSelBlock + threadIdx.x;
+    bool sel = false;
+    if (q < a.n) {
+        double err;
+        sel = select_pixel(a, q, &err);
+        if (a.err) a.err[q] = err;
+    }
+    const uint64_t m = __ballot(sel);
+    const uint32_t w = threadIdx.x / 64;
+    if ((threadIdx.x & 63) == 0) {
+        wc[w] = (uint32_t)__popcll(m);
+        if (q < a.n) a.masks[q / 64] = m;  // a wave's first pixel in range <=> the wave has pixels
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < kSelBlock / 64; ++k) t += wc[k];
+        a.block_counts[blockIdx.x] = t;
+    }
+}
+// Pass 2, ONE block: block_counts -> exclusive prefix sums in place, the total -> *n_out.
+__global__ __launch_bounds__(kSelBlock) void select_scan_kernel(SelectArgs a) {
+    __shared__ uint32_t wt[kSelBlock / 64];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x / 64;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < a.n_blocks; base += kSelBlock) {
+        const uint32_t k = base + threadIdx.x;
+        const uint32_t v = k < a.n_blocks ? a.block_counts[k] : 0u;
+        uint32_t inc = v;  // inclusive scan within the wave
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(inc, off, 64);
+            if (lane >= (uint32_t)off) inc += o;
+        }
+        if (lane == 63) wt[w] = inc;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kSelBlock / 64; ++j) {
+            before += j < w ? wt[j] : 0u;
+            total += wt[j];
+        }
+        if (k < a.n_blocks) a.block_counts[k] = carry + before + inc - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *a.n_out = carry;
+}
+// Pass 3: a selected pixel's position is its block's offset + the selected pixels of the block's
+// earlier waves + those of the wave's earlier lanes (mbcnt): ascending order.
+__global__ __launch_bounds__(kSelBlock) void select_scatter_kernel(SelectArgs a) {
+    __shared__ uint32_t wc[kSelBlock / 64];
+    const uint32_t q = blockIdx.x * kSelBlock + threadIdx.x;
+    const uint32_t w = threadIdx.x / 64;
+    const uint64_t m = q < a.n ? a.masks[q / 64] : 0ull;
+    if ((threadIdx.x & 63) == 0) wc[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t pos = a.block_counts[blockIdx.x];
+#pragma unroll
+    for (uint32_t j = 0; j < kSelBlock / 64; ++j) pos += j < w ? wc[j] : 0u;
+    if (q < a.n && ((m >> (threadIdx.x & 63)) & 1ull)) a.list[pos + rank_in(m)] = q;
+}
+
+// rt_accum_resolve_counts: resolve_kernel with a per-pixel scale 1.0 / counts[q] (camera.zig:284),
+// 0 for a pixel without samples.
+template <int kOut>
+__global__ __launch_bounds__(256) void resolve_counts_kernel(const double* __restrict__ accum,
+                                                             const uint32_t* __restrict__ counts, uint64_t n_pixels,
+                                                             void* __restrict__ out) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n_pixels) return;
+    const uint32_t c = counts[q];
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (c != 0) {
+        const double scale = 1.0 / (double)c;
+        const double* a = accum + 3 * q;
+        x = a[0] * scale;
+        y = a[1] * scale;
+        z = a[2] * scale;
+    }
     if constexpr (kOut == 0) {
         double* o = (double*)out + 3 * q;
         o[0] = x;
@@ -2264,6 +2483,86 @@ extern "C" hipError_t rtk_launch_samples_fast(const rtk::KernelParams* p, const 
                                               hipStream_t stream, const char** name, bool direct,
                                               uint32_t* plan_waves) {
     return launch_bvh<true>(p, b, geo, mat, ua, stats, stream, name, direct, plan_waves);
+}
+
+// Gather passes: the gather twin of the direct-mode kernel launch_samples / launch_bvh would pick,
+// over the ua->n_units = L x n items of the pass (same LDS layout, same persistent grid).
+extern "C" hipError_t rtk_launch_gather(const rtk::KernelParams* p, const rtk::BvhArgs* b, bool fast,
+                                        const rtk::GeoRec* geo, const rtk::MatRec* mat, const rtk::UnitArgs* ua,
+                                        const rtk::GatherArgs* ga, void* stats, hipStream_t stream, const char** name) {
+    using namespace rtk;
+    const uint64_t total = ua->n_units;
+    if (total == 0) return hipSuccess;
+    if (ua->samples == nullptr || ga->counts == nullptr || ua->P == 0) return hipErrorInvalidValue;
+    auto* st = (unsigned long long*)stats;
+    if (b == nullptr) {
+        if (fast) return hipErrorInvalidValue;  // fast mode walks the tree
+        const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
+        const size_t shmem = (v.lds ? (size_t)p->n_pad * sizeof(GeoRec) : 0) + (kSeedWin ? (kBlock / 64) * kSeedWinBytes : 0);
+        const uint64_t need = (total + kBlock - 1) / kBlock;
+        auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+            const uint32_t blocks = grid_blocks(need, persistent_blocks(kernel, shmem), ua, kBlock);
+            if (name) *name = nm;
+            hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), shmem, stream, *p, geo, mat, *ua, st, *ga);
+            return hipGetLastError();
+        };
+        return v.lds ? launch(gather_kernel<true, 4, 1>, "lds_u4(gather)") : launch(gather_kernel<false, 4, 1>, "smem_u4(gather)");
+    }
+    if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
+    // the LDS shape of launch_bvh's uninstrumented kernels
+    const uint32_t block = (uint32_t)kBlockBvh;
+    const size_t scene_bytes = (size_t)bvh_leaves_offset(b->n_nodes) + (size_t)b->n_leaves * sizeof(BvhLeaf);
+    const bool refs16 = bvh_leaves_offset(b->n_nodes) < 32768u && (size_t)b->n_leaves * sizeof(BvhLeaf) < 32768u;
+    const size_t lds_entry = refs16 ? sizeof(StackEntry) : sizeof(int32_t);
+    const bool lds_scene = (size_t)b->stack_depth * block * lds_entry + scene_bytes <= kLdsSceneBudget &&
+                           (sizeof(StackEntry) == sizeof(int32_t) || refs16);
+    const size_t stack_bytes = (size_t)b->stack_depth * block * (lds_scene ? sizeof(StackEntry) : sizeof(int32_t));
+    const size_t shmem = (((lds_scene ? scene_bytes : 0) + stack_bytes + 15) & ~(size_t)15) + (!lds_scene ? 0 : kSeedWinBlockBytes);
+    const uint64_t need = (total + block - 1) / block;
+    auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+        uint32_t cap32 = 0;
+        const hipError_t ea = rtk_resident_blocks((const void*)kernel, (int)block, shmem, &cap32);
+        if (ea != hipSuccess) return ea;
+        const uint32_t blocks = grid_blocks(need, cap32, ua, block);
+        if (name) *name = nm;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(block), shmem, stream, *p, *b, geo, mat, *ua, st, *ga);
+        return hipGetLastError();
+    };
+    if (fast)
+        return lds_scene ? launch(gather_kernel_fast<true>, "fast_f32_lds(gather)")
+                         : launch(gather_kernel_fast<false>, "fast_f32_global(gather)");
+    return lds_scene ? launch(gather_kernel_bvh<true>, "bvh_lds(gather)") : launch(gather_kernel_bvh<false>, "bvh_global(gather)");
+}
+
+extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, hipStream_t stream) {
+    using namespace rtk;
+    if (a->L == 0 || a->n == 0 || a->samples == nullptr || a->sums == nullptr || a->counts == nullptr)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_reduce_kernel, dim3((a->L + 255) / 256), dim3(256), 0, stream, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_select(const rtk::SelectArgs* a, hipStream_t stream) {
+    using namespace rtk;
+    if (a->n == 0 || a->n_blocks != (a->n + kSelBlock - 1) / kSelBlock || !a->accum || !a->m2 || !a->counts ||
+        !a->block_counts || !a->masks || !a->list || !a->n_out)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(select_count_kernel, dim3(a->n_blocks), dim3(kSelBlock), 0, stream, *a);
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(kSelBlock), 0, stream, *a);
+    hipLaunchKernelGGL(select_scatter_kernel, dim3(a->n_blocks), dim3(kSelBlock), 0, stream, *a);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t rtk_launch_resolve_counts(const double* accum, const uint32_t* counts, uint64_t n_pixels,
+                                                uint32_t format, void* out, hipStream_t stream) {
+    using namespace rtk;
+    if (!accum || !counts || !out || n_pixels == 0 || n_pixels >= (1ull << 32)) return hipErrorInvalidValue;
+    const uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
+    if (format == 0)
+        hipLaunchKernelGGL(resolve_counts_kernel<0>, dim3(blocks), dim3(256), 0, stream, accum, counts, n_pixels, out);
+    else
+        hipLaunchKernelGGL(resolve_counts_kernel<1>, dim3(blocks), dim3(256), 0, stream, accum, counts, n_pixels, out);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t rtk_launch_fold_rest(const rtk::FoldArgs* f, hipStream_t stream) {

@@ -156,6 +156,8 @@ struct rt_context {
     size_t sched_acc_bytes = 0;
     uint64_t sched_lanes = 0;       // resident lanes the schedule is sized for (CUs x 16 waves x 64)
     unsigned long long* d_ctr = nullptr;  // rtk::kCtrBytes, zeroed per launch ([kErrWord]: error word)
+    void* d_select = nullptr;       // rt_accum_select's scratch: block counts + wave ballots (rt_kernel.h)
+    size_t select_bytes = 0;
     const char* last_kernel = "sample_kernel";
     SceneData scene;                // host copy (BVH rebuilds for far-away cameras, scene comparisons)
     rtk::BvhArgs bvh{};
@@ -767,7 +769,7 @@ int rt_context_destroy(rt_context* ctx) {
         (void)hipDeviceSynchronize();
     }
     for (void* p : {(void*)ctx->d_geo, (void*)ctx->d_mat, (void*)ctx->d_ring, (void*)ctx->d_sums, (void*)ctx->d_flags,
-                    (void*)ctx->d_samples, (void*)ctx->d_samples2, (void*)ctx->d_fold_ctr, (void*)ctx->d_sched, (void*)ctx->d_sched_acc, (void*)ctx->d_ctr, (void*)ctx->d_nodes, (void*)ctx->d_leaves, (void*)ctx->d_always_geo,
+                    (void*)ctx->d_samples, (void*)ctx->d_samples2, (void*)ctx->d_fold_ctr, (void*)ctx->d_sched, (void*)ctx->d_sched_acc, (void*)ctx->d_ctr, ctx->d_select, (void*)ctx->d_nodes, (void*)ctx->d_leaves, (void*)ctx->d_always_geo,
                     (void*)ctx->d_always_sid, ctx->d_out, (void*)ctx->d_stats})
         (void)hipFree(p);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
@@ -1158,6 +1160,197 @@ int rt_accum_resolve(rt_context* ctx, const void* d_accum, uint64_t n_pixels, ui
     return RT_OK;
 }
 
+// ---- adaptive sampling (rt.h) ---------------------------------------------------
+// A gather pass: direct mode over the listed pixels, in as many sub-passes as the sample buffer's cap
+// asks for.  Every sub-pass is a gather sample kernel (which reads each pixel's count for its stream
+// keys) and the gather reduce pass (which adds the stored colours and advances the counts), both on
+// `stream`: the counts carry the position from one sub-pass to the next.
+int rt_render_pixels_accumulate(rt_context* ctx, const rt_camera* cam, const uint32_t* d_pixels, uint32_t n_pixels,
+                                uint32_t sample_count, void* d_accum, void* d_m2, uint32_t* d_counts, void* d_stats,
+                                void* stream) {
+    // the argument checks that need no context come first, the context last: each answers before
+    // anything touches a device
+    if (!cam) { rt_set_last_error("null camera"); return RT_ERR_INVALID; }
+    if (!d_accum) { rt_set_last_error("null accumulator"); return RT_ERR_INVALID; }
+    if (!d_counts) { rt_set_last_error("null counts"); return RT_ERR_INVALID; }
+    rt_camera c = *cam;  // samples_per_pixel / pixel_samples_scale are unused by the contract
+    c.samples_per_pixel = sample_count ? sample_count : 1;
+    c.pixel_samples_scale = 1.0;
+    int rc = validate_camera(&c);
+    if (rc) return rc;
+    const uint64_t WH = (uint64_t)c.image_width * c.image_height;
+    if (!d_pixels && n_pixels != WH) {
+        rt_set_last_error("a null pixel list means every pixel: n_pixels must be image_width * image_height");
+        return RT_ERR_INVALID;
+    }
+    if (n_pixels > WH) { rt_set_last_error("n_pixels exceeds image_width * image_height"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (ctx->profile) {
+        rt_set_last_error("gather passes have no instrumented kernel (rt_context_enable_profile is on)");
+        return RT_ERR_INVALID;
+    }
+    if (sample_count == 0 || n_pixels == 0) return RT_OK;
+    if (ctx->n_spheres == 0) { rt_set_last_error("no scene uploaded"); return RT_ERR_INVALID; }
+    const uint64_t L = n_pixels;
+    // the pass's sample buffer, L x n x 24 B, under direct mode's cap; RTZIG_GATHER_BYTES lowers it
+    // (read per call: the tests force the split at small shapes)
+    uint64_t cap = rtk::kDirectBytes;
+    if (const char* e = std::getenv("RTZIG_GATHER_BYTES")) {
+        const unsigned long long v = std::strtoull(e, nullptr, 10);
+        if (v > 0 && v < cap) cap = v;
+    }
+    const uint64_t per_sample = L * 3 * sizeof(double);
+    if (per_sample > cap) {
+        rt_set_last_error("one sample of the pixel list does not fit the pass's sample buffer");
+        return RT_ERR_CAPACITY;
+    }
+    // samples per sub-pass: within the cap, and fewer than 2^32 items
+    const uint32_t n_per = (uint32_t)std::min<uint64_t>({(uint64_t)sample_count, cap / per_sample, 0xffffffffull / L});
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    if (needs_far_rebuild(ctx->scene, c)) {
+        rc = quiesce(ctx);  // the previous render may still walk the old tree
+        if (rc) return rc;
+        build_bvh(ctx->scene, far_bound(ctx->scene, c));
+        rc = upload_bvh(ctx);
+        if (rc) return rc;
+    }
+    if (needs_training(ctx->scene, c, L * sample_count)) {
+        rc = quiesce(ctx);
+        if (rc) return rc;
+        train_bvh(ctx->scene, c);
+        rc = upload_bvh(ctx);
+        if (rc) return rc;
+    }
+    rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    // the workspace of direct mode, one sample buffer (rt.h "Workspace").  A larger buffer is kept as it
+    // is: an adaptive loop's lists shrink from round to round, and giving memory back every time the
+    // need falls by a quarter would cost each round a host wait and a reallocation (the next row
+    // render applies the give-back rule)
+    if (!rc) rc = release_buffer(ctx, (void**)&ctx->d_ring, &ctx->ring_bytes);
+    if (!rc) rc = release_buffer(ctx, (void**)&ctx->d_sums, &ctx->sums_bytes);
+    ctx->ring_waves = 0;
+    if (!rc) rc = ensure_buffer(ctx, (void**)&ctx->d_samples, &ctx->samples_bytes, (size_t)(per_sample * n_per));
+    if (!rc) rc = release_buffer(ctx, (void**)&ctx->d_samples2, &ctx->samples2_bytes);
+    ctx->samples_flip = 0;
+    if (!rc && !ctx->d_ctr) {
+        size_t cb = 0;
+        rc = ensure_buffer(ctx, (void**)&ctx->d_ctr, &cb, rtk::kCtrBytes);
+        if (!rc) HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrBytes, s));  // as render_rows: on the launch stream
+    }
+    if (rc) return rc;
+    const bool bvh = use_bvh(ctx);
+    const uint32_t n_sub = (sample_count + n_per - 1) / n_per;
+    // timing: one slot of the event log per sub-pass (at most kMaxTimed of them are timed)
+    const uint32_t n_timed = ctx->timing ? std::min(n_sub, kMaxTimed) : 0u;
+    if (n_timed) {
+        if (ctx->log_used + n_timed > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
+        ctx->call_first = ctx->log_used;
+        ctx->log_used += n_timed;
+        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
+            hipEvent_t e;
+            HIP_CHECK(make_event(&e, true));
+            ctx->events.push_back(e);
+        }
+        ctx->timed_calls = n_timed;
+    }
+    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
+    if (ctx->reduced_valid[0]) HIP_CHECK(hipStreamWaitEvent(s, ctx->reduced[0], 0));
+    rtk::KernelParams p = make_params(&c, 0, 1, c.image_height, ctx->n_spheres);
+    const rtk::GatherArgs ga{d_pixels, d_counts};
+    uint32_t left = sample_count;
+    for (uint32_t k = 0; k < n_sub; k++) {
+        const uint32_t n = std::min(left, n_per);
+        left -= n;
+        p.s_begin = 0;
+        p.s_count = n;
+        rtk::UnitArgs ua;
+        std::memset(&ua, 0, sizeof ua);
+        ua.samples = ctx->d_samples;
+        ua.ctr = ctx->d_ctr;
+        ua.P = (uint32_t)L;
+        ua.spp = n;
+        ua.n_units = (uint32_t)(L * n);
+        ua.div_p = rtk::fastdiv_make((uint32_t)L);
+        ua.div_tiles = rtk::fastdiv_make(1);
+        ua.stall_ticks = stall_bound(bvh, ctx->n_spheres);
+        ua.scale = 1.0;
+        HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrLaunchBytes, s));  // not the sticky error word
+        hipEvent_t* ev = k < n_timed ? &ctx->events[kEventsPerCall * (ctx->call_first + k)] : nullptr;
+        if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+        HIP_CHECK(rtk_launch_gather(&p, bvh ? &ctx->bvh : nullptr, bvh && ctx->precision == RT_PRECISION_F32, ctx->d_geo,
+                                    ctx->d_mat, &ua, &ga, d_stats, s, &ctx->last_kernel));
+        if (ev) HIP_CHECK(hipEventRecord(ev[1], s));
+        if (ev) HIP_CHECK(hipEventRecord(ev[2], s));
+        const rtk::GatherReduceArgs ra{ctx->d_samples, d_pixels, (double*)d_accum, (double*)d_m2, d_counts, (uint32_t)L, n};
+        HIP_CHECK(rtk_launch_gather_reduce(&ra, s));
+        if (ev) HIP_CHECK(hipEventRecord(ev[3], s));
+    }
+    HIP_CHECK(hipEventRecord(ctx->launched, s));
+    ctx->launched_valid = true;
+    ctx->launched_stream = s;
+    HIP_CHECK(hipEventRecord(ctx->reduced[0], s));
+    ctx->reduced_valid[0] = true;
+    HIP_CHECK(hipEventRecord(ctx->done, s));
+    ctx->done_valid = true;
+    return RT_OK;
+}
+
+int rt_accum_select(rt_context* ctx, const void* d_accum, const void* d_m2, const uint32_t* d_counts, uint64_t n_pixels,
+                    uint32_t min_count, uint32_t max_count, double tolerance, double floor, uint32_t* d_list,
+                    uint32_t* d_n, double* d_err, void* stream) {
+    if (!d_accum || !d_m2 || !d_counts || !d_list || !d_n) {
+        rt_set_last_error("null accumulator / m2 / counts / list / count output");
+        return RT_ERR_INVALID;
+    }
+    if (min_count < 2) { rt_set_last_error("min_count must be at least 2"); return RT_ERR_INVALID; }
+    if (max_count < min_count) { rt_set_last_error("max_count must be at least min_count"); return RT_ERR_INVALID; }
+    if (n_pixels >= (1ull << 32)) { rt_set_last_error("n_pixels must be below 2^32"); return RT_ERR_INVALID; }
+    if (!(floor > 0)) { rt_set_last_error("floor must be > 0"); return RT_ERR_INVALID; }
+    if (std::isnan(tolerance)) { rt_set_last_error("tolerance is NaN"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (n_pixels == 0) {
+        HIP_CHECK(hipMemsetAsync(d_n, 0, sizeof(uint32_t), s));
+        return RT_OK;
+    }
+    // the block-count / ballot scratch belongs to the context and grows as needed
+    int rc = ensure_buffer(ctx, &ctx->d_select, &ctx->select_bytes, rtk::select_scratch_bytes(n_pixels));
+    if (rc) return rc;
+    rtk::SelectArgs a{};
+    a.accum = (const double*)d_accum;
+    a.m2 = (const double*)d_m2;
+    a.counts = d_counts;
+    a.n = (uint32_t)n_pixels;
+    a.min_count = min_count;
+    a.max_count = max_count;
+    a.n_blocks = (uint32_t)((n_pixels + rtk::kSelBlock - 1) / rtk::kSelBlock);
+    a.tolerance = tolerance;
+    a.floor = floor;
+    a.block_counts = (uint32_t*)ctx->d_select;
+    a.masks = (unsigned long long*)((char*)ctx->d_select + rtk::select_masks_offset(a.n_blocks));
+    a.list = d_list;
+    a.n_out = d_n;
+    a.err = d_err;
+    HIP_CHECK(rtk_launch_select(&a, s));
+    return RT_OK;
+}
+
+int rt_accum_resolve_counts(rt_context* ctx, const void* d_accum, const uint32_t* d_counts, uint64_t n_pixels,
+                            uint32_t output_format, void* d_out, void* stream) {
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (!d_accum || !d_out) { rt_set_last_error("null accumulator / output"); return RT_ERR_INVALID; }
+    if (!d_counts) { rt_set_last_error("null counts"); return RT_ERR_INVALID; }
+    if (output_format > RT_OUT_RGB8) { rt_set_last_error("bad output_format"); return RT_ERR_INVALID; }
+    if (n_pixels >= (1ull << 32)) { rt_set_last_error("n_pixels must be below 2^32"); return RT_ERR_INVALID; }
+    if (n_pixels == 0) return RT_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    HIP_CHECK(rtk_launch_resolve_counts((const double*)d_accum, d_counts, n_pixels, output_format, d_out,
+                                        (hipStream_t)stream));
+    return RT_OK;
+}
+
 int rt_context_fold_pending(rt_context* ctx, int* pending) {
     if (!ctx || !pending) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
     *pending = ctx->fold_pending ? 1 : 0;
@@ -1245,7 +1438,7 @@ int rt_context_workspace_bytes(rt_context* ctx, uint64_t* bytes) {
     if (!ctx || !bytes) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
     *bytes = (uint64_t)ctx->ring_bytes + ctx->sums_bytes + ctx->flags_bytes + ctx->samples_bytes + ctx->samples2_bytes +
              ctx->sched_bytes + ctx->sched_acc_bytes + (ctx->d_fold_ctr ? 2 * 16 * sizeof(unsigned long long) : 0) +
-             (ctx->d_ctr ? rtk::kCtrBytes : 0);
+             (ctx->d_ctr ? rtk::kCtrBytes : 0) + ctx->select_bytes;
     return RT_OK;
 }
 

@@ -154,6 +154,14 @@ class Camera:
                                             precision=precision):
             yield done, PPM(self.width, self.height, img)
 
+    def render_adaptive(self, min_spp, max_spp, step, tolerance, floor=0.01, device=0, output="linear",
+                        precision="f64", on_round=None):
+        """(PPM, counts) of render_adaptive: samples go where the noise estimate asks for them;
+        samplesPerPixel of the camera is not used."""
+        img, counts = render_adaptive(self.cam, self.scene.world, min_spp, max_spp, step, tolerance, floor=floor,
+                                      device=device, output=output, precision=precision, on_round=on_round)
+        return PPM(self.width, self.height, img), counts
+
 
 _PRECISION = {"f64": abi.RT_PRECISION_F64, "f32": abi.RT_PRECISION_F32}
 
@@ -223,6 +231,86 @@ def render_progressive(cam, spheres, passes, device=0, output="linear", precisio
         r.close()
 
 
+def _adaptive_args(min_spp, max_spp, step, tolerance, floor, output):
+    """render_adaptive's argument checks (host only): the values as (min_spp, max_spp, step,
+    tolerance, floor)."""
+    if output not in ("linear", "rgb8"):
+        raise ValueError(output)
+    min_spp, max_spp, step = int(min_spp), int(max_spp), int(step)
+    tolerance, floor = float(tolerance), float(floor)
+    if min_spp < 2:
+        raise ValueError("min_spp must be at least 2 (the noise estimate needs two samples)")
+    if max_spp < min_spp:
+        raise ValueError("max_spp must be at least min_spp")
+    if max_spp >= 2 ** 32:
+        raise ValueError("max_spp must be below 2^32")
+    if step < 1:
+        raise ValueError("step must be at least 1")
+    if math.isnan(tolerance) or tolerance < 0:
+        raise ValueError("tolerance must be a number >= 0")
+    if not floor > 0:
+        raise ValueError("floor must be > 0")
+    return min_spp, max_spp, step, tolerance, floor
+
+
+def render_adaptive(cam, spheres, min_spp, max_spp, step, tolerance, floor=0.01, device=0, output="linear",
+                    precision="f64", on_round=None):
+    """Adaptive render on one GPU: every pixel gets min_spp samples; then, round after round, the
+    pixels whose noise estimate is still above `tolerance` (rt_accum_select: the standard error of
+    the pixel's mean luminance r + g + b, relative to max(mean, floor)) get `step` more — fewer in the
+    round that would pass max_spp — until none is selected.  Returns (image, counts): the image
+    (linear -> (H, W, 3) f64, rgb8 -> (H, W, 3) u8) and the (H, W) uint32 samples each pixel got.
+    Every pixel is, bit for bit, the pixel of a one-pass render at spp = its own count.
+
+    Each round reads the number of selected pixels back: one 4-byte copy and host sync per round.
+    on_round(round, list, accum, m2, counts) is called after each selection (the last one, which
+    selects nothing, included) with device tensors: the selected indices (int32, ascending), the
+    unscaled sums (W*H, 3), the squared-luminance sums (W*H) and the counts (W*H, int32) at that point.
+    cam.samples_per_pixel is not used."""
+    min_spp, max_spp, step, tolerance, floor = _adaptive_args(min_spp, max_spp, step, tolerance, floor, output)
+    import torch
+
+    W, H = cam.image_width, cam.image_height
+    n = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * n)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        r.set_precision(precision)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            accum = torch.empty((H * W, 3), dtype=torch.float64, device=dev)
+            m2 = torch.empty(H * W, dtype=torch.float64, device=dev)
+            counts = torch.zeros(H * W, dtype=torch.int32, device=dev)  # u32 on the device
+            lst = torch.empty(H * W, dtype=torch.int32, device=dev)
+            n_sel = torch.zeros(1, dtype=torch.int32, device=dev)
+            out = torch.empty((H, W, 3), dtype=torch.float64 if output == "linear" else torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            r.accumulate_pixels(cam, None, min_spp, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), stream_ptr=stream)
+            rnd = 0
+            while True:
+                r.select(accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), H * W, min_spp, max_spp, tolerance, floor,
+                         lst.data_ptr(), n_sel.data_ptr(), stream_ptr=stream)
+                k = int(n_sel.item())  # the round's host sync
+                if on_round is not None:
+                    on_round(rnd, lst[:k], accum, m2, counts)
+                if k == 0:
+                    break
+                # a pixel selected now was selected in every round before: all of the list stand at
+                # min_spp + rnd * step samples, so one clamp keeps every pixel within max_spp
+                more = min(step, max_spp - (min_spp + rnd * step))
+                r.accumulate_pixels(cam, lst.data_ptr(), more, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(),
+                                    n_pixels=k, stream_ptr=stream)
+                rnd += 1
+            r.resolve_counts(accum.data_ptr(), counts.data_ptr(), H * W, out.data_ptr(), output=output, stream_ptr=stream)
+            img = out.cpu().numpy()  # waits for the stream
+            cnt = counts.cpu().numpy().view(np.uint32).reshape(H, W)
+            r.sync()  # reports a failure the kernel recorded
+        return img, cnt
+    finally:
+        r.close()
+
+
 class DeviceRenderer:
     """Device-resident renderer for one GPU (rt_context): scene uploaded once, rows rendered into
     device memory (e.g. a torch tensor's data_ptr) on a caller-provided HIP stream."""
@@ -232,6 +320,7 @@ class DeviceRenderer:
         self.ctx = C.c_void_p()
         check("rt_context_create", self.lib.rt_context_create(device, C.byref(self.ctx)))
         self.device = device
+        self._pixels_keep = None  # the device copy of accumulate_pixels' last list
 
     def set_scene(self, spheres):
         n = len(spheres)
@@ -284,6 +373,79 @@ class DeviceRenderer:
         check("rt_accum_resolve",
               self.lib.rt_accum_resolve(self.ctx, C.c_void_p(d_accum_ptr or 0), n_pixels, n_samples, fmt,
                                         C.c_void_p(d_out_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def _pixel_list(self, cam, pixels, n_pixels):
+        """(device pointer, length) of a pixel list for accumulate_pixels.  None: every pixel.  An int is
+        a raw device pointer to uint32 indices, taken on trust (n_pixels gives its length).  A host
+        array / sequence or a torch tensor is validated first — every index in [0, W*H), no index
+        twice — and, if it is not a 32-bit integer tensor on this device already, copied there."""
+        wh = cam.image_width * cam.image_height
+        if pixels is None:
+            return 0, wh if n_pixels is None else int(n_pixels)
+        if isinstance(pixels, int):
+            if n_pixels is None:
+                raise ValueError("a raw pixel-list pointer needs n_pixels")
+            return pixels, int(n_pixels)
+        import torch
+
+        if isinstance(pixels, torch.Tensor):
+            t = pixels.reshape(-1)
+            if t.dtype not in (torch.int32, torch.int64):
+                raise TypeError("pixel list: an int32 or int64 tensor")
+        else:
+            a = np.asarray(pixels).reshape(-1)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise TypeError("pixel list: integers")
+            t = torch.from_numpy(a.astype(np.int64))
+        n = t.numel()
+        if n_pixels is not None and int(n_pixels) != n:
+            raise ValueError("n_pixels differs from the list's length")
+        if n:
+            if int(t.min()) < 0 or int(t.max()) >= wh:
+                raise ValueError("pixel list: an index outside [0, image_width * image_height)")
+            if torch.unique(t).numel() != n:
+                raise ValueError("pixel list: an index appears twice")
+        dev = torch.device("cuda", self.device)
+        if t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+            t = t.to(device=dev, dtype=torch.int32).contiguous()
+        self._pixels_keep = t  # alive until the next list replaces it (the pass is asynchronous)
+        return t.data_ptr(), n
+
+    def accumulate_pixels(self, cam, pixels, sample_count, d_accum_ptr, d_m2_ptr, d_counts_ptr, n_pixels=None,
+                          d_stats_ptr=None, stream_ptr=None):
+        """rt_render_pixels_accumulate: sample_count more samples for the listed pixels (`pixels`: None
+        for every pixel, a host array or torch tensor of indices j*W + i — validated: in range, no
+        duplicates — or a raw device pointer with n_pixels, taken on trust), each continuing at its own
+        count d_counts[p]; their colours are added in sample order to d_accum[p] (W*H x 3 f64), their
+        squared luminances to d_m2[p] (W*H f64, or None), and d_counts[p] (W*H u32) advances.  Every
+        pixel then holds the sums of a one-pass render at its own count."""
+        ptr, n = self._pixel_list(cam, pixels, n_pixels)
+        if n == 0 and pixels is not None:
+            return  # an empty list: nothing to do (a null pointer would mean every pixel)
+        check("rt_render_pixels_accumulate",
+              self.lib.rt_render_pixels_accumulate(self.ctx, C.byref(cam), C.c_void_p(ptr), n, sample_count,
+                                                   C.c_void_p(d_accum_ptr or 0), C.c_void_p(d_m2_ptr or 0),
+                                                   C.c_void_p(d_counts_ptr or 0), C.c_void_p(d_stats_ptr or 0),
+                                                   C.c_void_p(stream_ptr or 0)))
+
+    def select(self, d_accum_ptr, d_m2_ptr, d_counts_ptr, n_pixels, min_count, max_count, tolerance, floor,
+               d_list_ptr, d_n_ptr, d_err_ptr=None, stream_ptr=None):
+        """rt_accum_select: the pixels that need more samples (count < min_count, or count < max_count
+        and not err <= tolerance; err = standard error of the mean luminance / max(mean, floor)), in
+        ascending order into d_list (n_pixels u32), their number into d_n (one u32); d_err (n_pixels
+        f64, optional) receives every pixel's err.  All device pointers; asynchronous."""
+        check("rt_accum_select",
+              self.lib.rt_accum_select(self.ctx, C.c_void_p(d_accum_ptr or 0), C.c_void_p(d_m2_ptr or 0),
+                                       C.c_void_p(d_counts_ptr or 0), n_pixels, min_count, max_count, tolerance,
+                                       floor, C.c_void_p(d_list_ptr or 0), C.c_void_p(d_n_ptr or 0),
+                                       C.c_void_p(d_err_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def resolve_counts(self, d_accum_ptr, d_counts_ptr, n_pixels, d_out_ptr, output="linear", stream_ptr=None):
+        """rt_accum_resolve_counts: d_out[p] = d_accum[p] * (1 / d_counts[p]) (0 without samples)."""
+        fmt = abi.RT_OUT_LINEAR_F64 if output == "linear" else abi.RT_OUT_RGB8
+        check("rt_accum_resolve_counts",
+              self.lib.rt_accum_resolve_counts(self.ctx, C.c_void_p(d_accum_ptr or 0), C.c_void_p(d_counts_ptr or 0),
+                                               n_pixels, fmt, C.c_void_p(d_out_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
     def flush(self):
         """Runs a pending deferred reduce pass (rt_context_flush)."""

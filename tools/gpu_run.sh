@@ -23,6 +23,10 @@
 #   progressive  config 4 accumulated in 1 / 10 / 50 passes with a resolve after each: wall time and the
 #              per-pass overhead (tools/progressive_cost.py; its JSON on stdout is kept as
 #              profiles/progressive/cost.json)
+#   adaptive   what adaptive sampling costs on config 4: gather passes against row passes, sparse lists,
+#              select / resolve, one render_adaptive run (tools/adaptive_cost.py; its JSON on stdout is
+#              kept as profiles/adaptive/cost.json).  Its GPU tests (tests/test_gpu_adaptive.py) run
+#              with the `tests` step
 #   peak       event-timed VALU peak and issue-cost table (tools/bin/peak_rates, built beforehand)
 #   diag       bounds-checked builds through tools/diag_modes.py (ab/bounds*.so)
 #   uselib     copy $LIB (an ab/*.so build) over the in-tree librtzig.so for the steps after it (on the
@@ -57,6 +61,7 @@ for step in "$@"; do
     configs) run configs 300 python3 -u tools/configs_bench.py --out "gpurun_out/configs_$T.json" ;;
     dropin)  run dropin 300 python3 -u tools/dropin_cold.py --runs 3 --configs ${DROPIN_CONFIGS:-2,4,5} ;;
     progressive) run progressive 200 python3 -u tools/progressive_cost.py ;;
+    adaptive) run adaptive 300 python3 -u tools/adaptive_cost.py ;;
     peak)    run peak 300 ./tools/bin/peak_rates ${PEAK_MS:-60} ${PEAK_MODE:-2} ;;
     diag)    run diag 300 python3 -u tools/diag_modes.py raytracing-with-zig_amd/librtzig.so ab/bounds.so --oracle-row ;;
     uselib)  cp "$LIB" raytracing-with-zig_amd/librtzig.so || exit 2; echo "== using $LIB" ;;
