@@ -273,6 +273,51 @@ int rt_accum_select(rt_context* ctx, const void* d_accum, const void* d_m2,
  * d_counts). */
 int rt_accum_resolve_counts(rt_context* ctx, const void* d_accum, const uint32_t* d_counts,
                             uint64_t n_pixels, uint32_t output_format, void* d_out, void* stream);
+/* ---- feature buffers: first-hit albedo, normal, depth and coverage per pixel ---
+ * The auxiliary buffers a denoiser or compositor is guided by, accumulated like colour.  For pixel
+ * p = j*W + i and sample s the feature ray is the ray getRay (camera.zig:187-215) produces from the
+ * stream rt_sample_key(seed, p, s): two sampleSquare draws, then the defocus disk's rejection draws
+ * when defocus_angle > 0 — bit for bit the camera ray of colour sample s in a parity (f64) render.
+ * Its closest hit in (t_min, t_max) is HittableList.hit's (ties: the lower sphere index).  A sample
+ * that hits contributes
+ *   albedo: the attenuation scatter would apply — the sphere's albedo for Lambertian and Metal
+ *           (material.zig:27-39, 55-68), (1, 1, 1) for Dielectric (:82-110); no random draw is made;
+ *   normal: the hit record's normal after setFaceNormal (sphere.zig:44-53):
+ *           outward = (point - center) * inv_r, negated when dot(dir, outward) >= 0;
+ *   depth:  the Euclidean distance t * sqrt(lenSquared(dir)), lenSquared = (x*x + y*y) + z*z, a
+ *           correctly rounded sqrt, no fused multiply-add;
+ *   hit:    1.
+ * A sample that misses contributes exactly nothing (the sky is an analytic function of the ray; a
+ * colour render at bounce_max = 1 gives its per-pixel mean).  Per pixel the samples' values are
+ * added, in sample order, to UNSCALED sums in DEVICE memory, indexed by the local pixel k*W + i of
+ * rows j = row0 + k*row_step, k < n_rows: d_albedo [P][3] f64, d_normal [P][3] f64, d_depth [P] f64,
+ * d_hits [P] u32.  d_albedo and d_normal have the layout of the colour accumulator:
+ * rt_accum_resolve scales them or packs them to RGB8.  Mean depth is depth / hits, coverage
+ * hits / samples.
+ *
+ * sample_begin == 0 starts a new image: the buffers are overwritten, not read, and need not be
+ * initialised.  sample_begin > 0 continues from the stored sums.  Any split of [0, n) into
+ * consecutive calls leaves, in all four buffers, the bits of the one call [0, n); the result does
+ * not depend on row_step, on which walk ran or on which tree the context holds.  Each of the four
+ * pointers may be NULL: that buffer is skipped.  All four NULL: RT_OK, no launch.
+ * sample_count == 0 or n_rows == 0: RT_OK, nothing is touched.  RT_ERR_INVALID: null ctx or cam; a
+ * row range past the image; sample_begin + sample_count > 2^32 - 1.  cam->samples_per_pixel,
+ * pixel_samples_scale and bounce_max are not used.
+ *
+ * Precision: the pass always uses parity arithmetic and the parity stream, whatever
+ * rt_context_set_precision says — on an RT_PRECISION_F32 context the feature rays are those of the
+ * f64 render, not of the fast render's own stream.  Instrumented contexts are accepted; the pass
+ * has no instrumented form and writes no stats.
+ *
+ * Launch: asynchronous on `stream`, one kernel, a plain one-stream call (a pending deferred reduce
+ * pass runs first).  It walks the structure the context holds now (rt_context_tree_info) and never
+ * rebuilds or retrains the BVH; it uses no per-sample workspace.  rt_context_kernel_times reports
+ * the pass as sample_ms, with reduce_ms 0.  Passes on one set of buffers must be ordered. */
+int rt_render_rows_features(rt_context* ctx, const rt_camera* cam,
+                            uint32_t row0, uint32_t row_step, uint32_t n_rows,
+                            uint32_t sample_begin, uint32_t sample_count,
+                            void* d_albedo, void* d_normal, void* d_depth, uint32_t* d_hits,
+                            void* stream);
 /* Runs a pending deferred reduce pass (on the out_stream of the call that deferred it); no-op otherwise. */
 int rt_context_flush(rt_context* ctx);
 /* *pending = 1 if the last deferred call left its output pending (direct mode), else 0. */

@@ -143,6 +143,25 @@ struct GatherReduceArgs {
     uint32_t* counts;          // [W * H]
     uint32_t L, n;
 };
+// Feature passes (rt_render_rows_features): per launch-local pixel q = k * W + i, the
+// unscaled sums over the pass's samples of the camera ray's first-hit albedo, shading normal and
+// Euclidean depth, and the number of samples that hit.  Each pointer may be nullptr (that buffer is
+// neither read nor written).  The pass's samples are KernelParams::s_begin / s_count; s_begin == 0
+// overwrites, s_begin > 0 continues from the stored sums.  The feature kernels (feature_kernel*,
+// rt_kernel.hip) take this as a LAST kernel argument, so the kernarg offsets the shared code reads
+// stay put.
+struct FeatureArgs {
+    double* albedo;            // [P][3]
+    double* normal;            // [P][3]
+    double* depth;             // [P]
+    uint32_t* hits;            // [P]
+    unsigned long long* ctr;   // kCtrBytes: [kErrWord] error word (RTZIG_BOUNDS debug builds)
+    uint32_t P;                // pixels of the launch
+    // set by rtk_launch_features: 2^spread lanes trace a pixel's samples (0: one lane per pixel, its
+    // samples one after the other; 2 or 4: small launches — the kernel instantiation launched is the
+    // one compiled for it), and the tiles of 64 >> spread pixels, a wave each
+    uint32_t spread, n_tiles;
+};
 // rt_accum_select: an ordered stream compaction in three launches, none of which
 // waits on another block.  Blocks of kSelBlock threads, one pixel each.  Scratch (the context's):
 // [blocks] u32 block counts (the scan turns them into exclusive offsets in place), then, 8-B aligned,
@@ -351,6 +370,12 @@ extern "C" hipError_t rtk_launch_gather(const rtk::KernelParams* p, const rtk::B
                                         const rtk::GeoRec* geo, const rtk::MatRec* mat, const rtk::UnitArgs* ua,
                                         const rtk::GatherArgs* ga, void* stats, hipStream_t stream, const char** name);
 extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, hipStream_t stream);
+// Feature passes (rtk::FeatureArgs): the feature kernel of the structure the context holds — `b` ==
+// nullptr: the list walk; else the BVH walk, always in f64 — over the rows of `p` and its samples
+// [s_begin, s_begin + s_count).  One launch, no workspace.
+extern "C" hipError_t rtk_launch_features(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                          const rtk::MatRec* mat, const rtk::FeatureArgs* fa, hipStream_t stream,
+                                          const char** name);
 // rt_accum_select's three launches (count, scan, scatter) over a->n pixels.
 extern "C" hipError_t rtk_launch_select(const rtk::SelectArgs* a, hipStream_t stream);
 // out[q] = accum[q] * (1.0 / counts[q]) (0 where counts[q] == 0), formats as rtk_launch_resolve.

@@ -36,6 +36,13 @@
 //   select_count / select_scan / select_scatter_kernel the ordered selection of the pixels that need
 //   more samples, resolve_counts_kernel the resolve with a per-pixel scale.  The existing kernels
 //   compile to the same instructions as before.
+//
+// Feature buffers (rt_render_rows_features, rt_kernel.h FeatureArgs): feature_kernel (list walk) and
+//   feature_kernel_bvh run feature_loop, not path_loop — one lane per pixel (4 or 16 in small
+//   launches), its samples added in order, the camera ray's first hit only: sums of albedo, shading
+//   normal, depth and the hit count.  They reuse
+//   the camera functions and the walkers as they are; the existing kernels compile to the same
+//   instructions as before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -2058,6 +2065,196 @@ __global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) 
 #undef RTK_GATHER_ARGS
 #undef RTK_BVH_BODY
 
+// ------------------------------------------------------------------------------------------------
+// Feature passes (rt_render_rows_features, rt_kernel.h FeatureArgs): the first hit
+// of every camera ray, nothing after it.  A kernel family of its own, not a form of path_loop: one
+// lane per launch-local pixel, a wave per tile of 64 consecutive pixels (tiles strided over the
+// grid's waves: which wave takes a tile changes nothing).  The lane loops over the pass's samples in
+// sample order with the four sums in registers, loads them once when the pass continues an image and
+// stores them once at the end, so the additions are ordered without atomics and without a buffer.
+// A launch too small to fill the machine that way (FeatureArgs::spread > 0) gives a pixel K = 4 or 16
+// neighbouring lanes: they trace K consecutive samples at once, and every one of them then adds
+// the K values in sample order, read from the others by lane shuffles — the same additions in the
+// same order, K times the waves.
+// Per sample: the parity stream of (pixel, sample), getRay (camera_start, the defocus disk's rejection
+// draws as path_loop's trip body makes them, camera_finish), the walker's non-suspending closest hit,
+// and the hit record of path_loop's shading block.  No draw is made after the ray.
+// ------------------------------------------------------------------------------------------------
+template <int kL, class Walker>
+__device__ __forceinline__ void feature_loop(const KernelParams& p, const Walker& walk,
+                                             const GeoRec* __restrict__ geo_orig, const MatRec* __restrict__ mat_g,
+                                             const FeatureArgs& fa) {
+    const uint32_t W = p.width;
+    const uint32_t lane = lane_id();
+    const uint32_t waves = gridDim.x * (blockDim.x / 64);
+    // K = 2^kL lanes share a pixel (1 for launches that fill the machine with one
+    // lane per pixel): lane l traces pixel l / K of the tile, and in round r sample r * K + l % K
+    constexpr uint32_t kl = kL, K = 1u << kL;  // FeatureArgs::spread, compiled in
+    const uint32_t sub = lane & (K - 1), first = lane & ~(K - 1);
+    const uint32_t ppt = 64u >> kl;  // pixels per tile
+    Prof<0> pr;
+    // wave w of block b starts at tile w * blocks + b: a launch with fewer tiles than waves still puts
+    // a wave on every block (every CU), instead of filling a few blocks' waves and leaving CUs idle
+    for (uint32_t tile = (threadIdx.x / 64) * gridDim.x + blockIdx.x; tile < fa.n_tiles; tile += waves) {
+        // the last tile's lanes past the launch's last pixel trace that pixel again and store nothing
+        const uint32_t q0 = tile * ppt + (lane >> kl);
+        const bool live = q0 < fa.P;
+        const uint32_t q = live ? q0 : fa.P - 1;
+        const uint32_t row_local = fastdiv(q, p.div_width);
+        const uint32_t i = q - row_local * W;
+        const uint32_t j = p.row0 + row_local * p.row_step;
+        const uint64_t pixel = (uint64_t)j * W + i;
+        // every lane of a pixel holds the pixel's sums: all K make the same additions in the same order
+        double ax = 0.0, ay = 0.0, az = 0.0, nx = 0.0, ny = 0.0, nz = 0.0, dsum = 0.0;
+        uint32_t hits = 0;
+        if (p.s_begin != 0) {  // the pass continues an image: from the stored sums
+            if (fa.albedo) {
+                ax = fa.albedo[3 * (size_t)q];
+                ay = fa.albedo[3 * (size_t)q + 1];
+                az = fa.albedo[3 * (size_t)q + 2];
+            }
+            if (fa.normal) {
+                nx = fa.normal[3 * (size_t)q];
+                ny = fa.normal[3 * (size_t)q + 1];
+                nz = fa.normal[3 * (size_t)q + 2];
+            }
+            if (fa.depth) dsum = fa.depth[q];
+            if (fa.hits) hits = fa.hits[q];
+        }
+        const uint32_t rounds = (p.s_count - 1) / K + 1;  // s_count > 0; counted so that nothing wraps at 2^32
+        for (uint32_t rd = 0; rd < rounds; ++rd) {
+            const uint32_t s0 = rd * K;
+            // a lane past the pass's last sample traces that sample again; its values are not added
+            const bool on = sub < p.s_count - s0;
+            const uint32_t s = on ? s0 + sub : p.s_count - 1;
+            Rng g;
+            g.seed(sample_key(p.seed_mix, pixel, p.s_begin + s));
+            Ray r;
+            if (camera_start(i, j, g, r)) {
+                // randomInUnitDisk (vec.zig:82-92): path_loop's trip body for a camera ray
+                double ux, uy;
+                while (true) {
+                    ux = g.range_pm1();
+                    uy = g.range_pm1();
+                    const double xy = ux * ux + uy * uy;
+                    if (xy + 0.0 * 0.0 < 1) break;
+                }
+                camera_finish(ux, uy, r);
+            }
+            double t;
+            const int k = walk(r, p.t_min, p.t_max, &t, pr);
+            const bool hit = on && k >= 0 && bounds_ok((uint32_t)k < p.n_spheres, fa.ctr);
+            v3 alb = mk(0, 0, 0), nrm = mk(0, 0, 0);
+            double depth = 0.0;
+            if (hit) {
+                // hit record (sphere.zig:44-53), the operations of path_loop's shading block
+                const GeoRec sg = geo_orig[k];
+                const MatRec m = mat_g[k];
+                const v3 pt = r.orig + muls(r.dir, t);
+                const v3 outward = muls(pt - mk(sg.cx, sg.cy, sg.cz), m.inv_r);
+                const bool front = dot(r.dir, outward) < 0;
+                nrm = front ? outward : -outward;
+                // the attenuation scatter would apply: albedo (Lambertian, Metal), (1, 1, 1) (Dielectric)
+                const bool glass = m.kind > 1;
+                alb = mk(glass ? 1.0 : m.albedo[0], glass ? 1.0 : m.albedo[1], glass ? 1.0 : m.albedo[2]);
+                depth = t * sqrt_g(len_sq(r.dir));  // Euclidean distance to the hit point
+            }
+            if constexpr (K == 1) {
+                if (hit) {
+                    ax = ax + alb.x;
+                    ay = ay + alb.y;
+                    az = az + alb.z;
+                    nx = nx + nrm.x;
+                    ny = ny + nrm.y;
+                    nz = nz + nrm.z;
+                    dsum = dsum + depth;
+                    ++hits;
+                }
+            } else {
+                // the round's K samples of the pixel, taken from its lanes in sample order (all 64 lanes
+                // are here: the loops above are wave-uniform); one sum at a time, so that one shuffled
+                // value is live.  A sample that misses contributes exactly nothing.
+                const uint64_t hm = __ballot(hit) >> first;  // bit kk: the pixel's sample s0 + kk hit
+#define RTK_FEATURE_ADD(sum, v)                                      \
+    _Pragma("unroll") for (uint32_t kk = 0; kk < K; ++kk) {          \
+        const double o = __shfl(v, (int)(first + kk), 64);           \
+        if ((hm >> kk) & 1) sum = sum + o;                           \
+    }
+                RTK_FEATURE_ADD(ax, alb.x)
+                RTK_FEATURE_ADD(ay, alb.y)
+                RTK_FEATURE_ADD(az, alb.z)
+                RTK_FEATURE_ADD(nx, nrm.x)
+                RTK_FEATURE_ADD(ny, nrm.y)
+                RTK_FEATURE_ADD(nz, nrm.z)
+                RTK_FEATURE_ADD(dsum, depth)
+#undef RTK_FEATURE_ADD
+                hits += (uint32_t)__popcll(hm & ((1ull << K) - 1));
+            }
+        }
+        if (live && sub == 0) {
+            if (fa.albedo) {
+                fa.albedo[3 * (size_t)q] = ax;
+                fa.albedo[3 * (size_t)q + 1] = ay;
+                fa.albedo[3 * (size_t)q + 2] = az;
+            }
+            if (fa.normal) {
+                fa.normal[3 * (size_t)q] = nx;
+                fa.normal[3 * (size_t)q + 1] = ny;
+                fa.normal[3 * (size_t)q + 2] = nz;
+            }
+            if (fa.depth) fa.depth[q] = dsum;
+            if (fa.hits) fa.hits[q] = hits;
+        }
+    }
+}
+
+// The list walk (scenes of at most 8 spheres, or without a tree): geometry in LDS or by scalar loads,
+// as sample_kernel.
+template <bool kLds, int U, int kL>
+__global__ __launch_bounds__(kBlock) void feature_kernel(KernelParams p, const GeoRec* __restrict__ geo_g,
+                                                         const MatRec* __restrict__ mat_g, FeatureArgs fa) {
+    extern __shared__ GeoRec lds_geo[];
+    const GeoRec* geo = geo_g;
+    if constexpr (kLds) {
+        for (uint32_t k = threadIdx.x; k < p.n_pad; k += blockDim.x) lds_geo[k] = geo_g[k];
+        __syncthreads();
+        geo = lds_geo;
+    }
+    feature_loop<kL>(p, LinearWalker<U>{geo, p.n_pad, p.n_spheres}, geo_g, mat_g, fa);
+}
+
+// The BVH walk, tree staged in LDS (kLdsScene) or read from global memory; LDS layout as the sample
+// kernels' ([nodes][leaves] at address 0, then the per-lane stacks), without seed windows.  BvhArgs
+// is the second argument: the walker reads the always-list from the kernarg segment.
+template <bool kLdsScene, int kL>
+__global__ __launch_bounds__(kBlockBvh) void feature_kernel_bvh(KernelParams p, BvhArgs b,
+                                                                const GeoRec* __restrict__ geo_g,
+                                                                const MatRec* __restrict__ mat_g, FeatureArgs fa) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const size_t scene_bytes = kLdsScene ? (size_t)bvh_leaves_offset(b.n_nodes) + (size_t)b.n_leaves * sizeof(BvhLeaf) : 0;
+    using Stack = std::conditional_t<kLdsScene, StackEntry, int32_t>;
+    using Walker = BvhWalker<kLdsScene, kBlockBvh, Stack, false>;
+    Stack* stack = (Stack*)(lds_raw + scene_bytes);
+    stack[threadIdx.x] = (Stack)Walker::kEnd;  // entry 0 of this lane's stack: popping it ends the walk
+    const BvhNode* nodes = b.nodes;
+    const BvhLeaf* leaves = b.leaves;
+    if constexpr (kLdsScene) {
+        BvhNode* ln = (BvhNode*)lds_raw;
+        BvhLeaf* ll = (BvhLeaf*)(lds_raw + bvh_leaves_offset(b.n_nodes));
+        for (uint32_t k = threadIdx.x; k < b.n_nodes; k += blockDim.x) ln[k] = b.nodes[k];
+        for (uint32_t k = threadIdx.x; k < b.n_leaves; k += blockDim.x) ll[k] = b.leaves[k];
+        __syncthreads();
+        nodes = ln;
+        leaves = ll;
+    }
+    feature_loop<kL>(p, Walker{nodes, leaves, b.always_geo, b.always_sid, b.n_always, stack + threadIdx.x, b.origin_bound,
+                           geo_g, p.n_pad
+#if RTZIG_BOUNDS
+                           , b.n_nodes * (uint32_t)sizeof(BvhNode), (uint32_t)(b.n_leaves * sizeof(BvhLeaf)), b.stack_depth, fa.ctr
+#endif
+                 }, geo_g, mat_g, fa);
+}
+
 // Direct mode's second pass (rt_kernel.h "Work units"): thread q adds pixel q's stored colors in
 // sample order — pixelColor += rayColor(ray), camera.zig:133-136, from pixelColor = 0 — then
 // scales (:137) and writes linear f64 or the fused Color.toRgb bytes.  A wave's loads of one sample
@@ -2532,6 +2729,96 @@ extern "C" hipError_t rtk_launch_gather(const rtk::KernelParams* p, const rtk::B
         return lds_scene ? launch(gather_kernel_fast<true>, "fast_f32_lds(gather)")
                          : launch(gather_kernel_fast<false>, "fast_f32_global(gather)");
     return lds_scene ? launch(gather_kernel_bvh<true>, "bvh_lds(gather)") : launch(gather_kernel_bvh<false>, "bvh_global(gather)");
+}
+
+// Feature passes: the feature kernel of the structure launch_samples / launch_bvh would walk — `b` ==
+// nullptr: the list (the variant variant_choice picks); else the tree, in LDS under launch_bvh's own
+// condition for its uninstrumented kernels — over fa->n_tiles tiles of 64 pixels, a wave each, on at
+// most the resident grid.
+extern "C" hipError_t rtk_launch_features(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                          const rtk::MatRec* mat, const rtk::FeatureArgs* fa, hipStream_t stream,
+                                          const char** name) {
+    using namespace rtk;
+    if (fa->P == 0 || p->s_count == 0) return hipSuccess;
+    // lanes per pixel, 2^spread (FeatureArgs): one while a wave per 64 pixels fills the resident grid;
+    // else 4 or 16 (within the pass's samples), until the tiles do.  RTZIG_FEATURE_SPREAD=0|2|4
+    // forces the exponent (test hook: every form on the same inputs; any value gives the same bits)
+    FeatureArgs f = *fa;
+    auto set_spread = [&](uint64_t resident_waves) {
+        const uint64_t tiles64 = ((uint64_t)f.P + 63) / 64;
+        uint32_t kl = 0;  // the compiled forms: 1, 4 and 16 lanes per pixel
+        while (kl < 4 && (4u << kl) <= p->s_count && (tiles64 << kl) < resident_waves) kl += 2;
+        if (const char* e = std::getenv("RTZIG_FEATURE_SPREAD")) {
+            const int v = std::atoi(e);
+            if (v == 0 || v == 2 || v == 4) kl = (uint32_t)v;
+        }
+        const uint32_t ppt = 64u >> kl;
+        f.spread = kl;
+        f.n_tiles = (uint32_t)(((uint64_t)f.P + ppt - 1) / ppt);
+    };
+    // blocks: enough for a wave per tile, at least one per CU while tiles last (a small image would
+    // otherwise fill the waves of a few blocks: 400x225 pixels are 88 blocks of 1024 threads for 256
+    // CUs), at most the resident grid
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+        cus = 256;
+    auto grid_of = [&](uint64_t need, uint64_t cap) {
+        const uint64_t spread = f.n_tiles < (uint32_t)cus ? f.n_tiles : (uint64_t)cus;
+        const uint64_t g = need > spread ? need : spread;
+        return (uint32_t)(g < cap ? g : cap);
+    };
+    if (b == nullptr) {
+        const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
+        const size_t shmem = v.lds ? (size_t)p->n_pad * sizeof(GeoRec) : 0;
+        auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+            const uint64_t cap = persistent_blocks(kernel, shmem);
+            const uint64_t need = ((uint64_t)f.n_tiles + kBlock / 64 - 1) / (kBlock / 64);
+            if (name) *name = nm;
+            hipLaunchKernelGGL(kernel, dim3(grid_of(need, cap)), dim3(kBlock), shmem, stream, *p, geo, mat, f);
+            return hipGetLastError();
+        };
+        // the kernel's resident grid does not depend on the form: sized with the one-lane form's
+        set_spread((uint64_t)persistent_blocks(v.lds ? feature_kernel<true, 4, 0> : feature_kernel<false, 4, 0>, shmem) * (kBlock / 64));
+#define RTK_FEAT(L)                                                                                      \
+    if (f.spread == L)                                                                                   \
+        return v.lds ? launch(feature_kernel<true, 4, L>, "lds_u4(features)") : launch(feature_kernel<false, 4, L>, "smem_u4(features)");
+        RTK_FEAT(0) RTK_FEAT(2) RTK_FEAT(4)
+#undef RTK_FEAT
+        return hipErrorInvalidValue;
+    }
+    if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
+    // the tree goes to LDS exactly when launch_bvh's uninstrumented kernels hold it there
+    const uint32_t block = (uint32_t)kBlockBvh;
+    const size_t scene_bytes = (size_t)bvh_leaves_offset(b->n_nodes) + (size_t)b->n_leaves * sizeof(BvhLeaf);
+    const bool refs16 = bvh_leaves_offset(b->n_nodes) < 32768u && (size_t)b->n_leaves * sizeof(BvhLeaf) < 32768u;
+    const size_t lds_entry = refs16 ? sizeof(StackEntry) : sizeof(int32_t);
+    const bool lds_scene = (size_t)b->stack_depth * block * lds_entry + scene_bytes <= kLdsSceneBudget &&
+                           (sizeof(StackEntry) == sizeof(int32_t) || refs16);
+    const size_t stack_bytes = (size_t)b->stack_depth * block * (lds_scene ? sizeof(StackEntry) : sizeof(int32_t));
+    const size_t shmem = (lds_scene ? scene_bytes : 0) + stack_bytes;
+    auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+        uint32_t cap32 = 0;
+        const hipError_t ea = rtk_resident_blocks((const void*)kernel, (int)block, shmem, &cap32);
+        if (ea != hipSuccess) return ea;
+        const uint64_t need = ((uint64_t)f.n_tiles + block / 64 - 1) / (block / 64);
+        if (name) *name = nm;
+        hipLaunchKernelGGL(kernel, dim3(grid_of(need, cap32)), dim3(block), shmem, stream, *p, *b, geo, mat, f);
+        return hipGetLastError();
+    };
+    {
+        uint32_t cap0 = 0;  // the resident grid of the one-lane form sizes the spread
+        const hipError_t e0 = lds_scene ? rtk_resident_blocks((const void*)feature_kernel_bvh<true, 0>, (int)block, shmem, &cap0)
+                                        : rtk_resident_blocks((const void*)feature_kernel_bvh<false, 0>, (int)block, shmem, &cap0);
+        if (e0 != hipSuccess) return e0;
+        set_spread((uint64_t)cap0 * (block / 64));
+    }
+#define RTK_FEAT(L)                                                                                      \
+    if (f.spread == L)                                                                                   \
+        return lds_scene ? launch(feature_kernel_bvh<true, L>, "bvh_lds(features)") : launch(feature_kernel_bvh<false, L>, "bvh_global(features)");
+    RTK_FEAT(0) RTK_FEAT(2) RTK_FEAT(4)
+#undef RTK_FEAT
+    return hipErrorInvalidValue;
 }
 
 extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, hipStream_t stream) {

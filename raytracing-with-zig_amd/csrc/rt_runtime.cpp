@@ -1160,6 +1160,87 @@ int rt_accum_resolve(rt_context* ctx, const void* d_accum, uint64_t n_pixels, ui
     return RT_OK;
 }
 
+// ---- feature buffers (rt.h) -----------------------------------------------------
+// One launch of the feature kernel of the structure the context holds (use_bvh, as
+// rt_context_tree_info reports it), always in parity arithmetic; no workspace, no training.
+int rt_render_rows_features(rt_context* ctx, const rt_camera* cam, uint32_t row0, uint32_t row_step, uint32_t n_rows,
+                            uint32_t sample_begin, uint32_t sample_count, void* d_albedo, void* d_normal, void* d_depth,
+                            uint32_t* d_hits, void* stream) {
+    // the argument checks that need no context come first, the context last: each answers before
+    // anything touches a device.  An empty call checks what rt_render_rows_accumulate's does.
+    if (!cam) { rt_set_last_error("null camera"); return RT_ERR_INVALID; }
+    const bool empty = sample_count == 0 || n_rows == 0;
+    if (row_step == 0) row_step = 1;
+    if (!empty) {
+        if ((uint64_t)sample_begin + sample_count > 0xffffffffull) {
+            rt_set_last_error("sample_begin + sample_count exceeds 2^32 - 1");
+            return RT_ERR_INVALID;
+        }
+        rt_camera c = *cam;  // samples_per_pixel / pixel_samples_scale / bounce_max are unused by the contract
+        c.samples_per_pixel = 1;
+        const int rc = validate_camera(&c);
+        if (rc) return rc;
+        const uint64_t last_row = (uint64_t)row0 + (uint64_t)(n_rows - 1) * row_step;
+        if (last_row >= cam->image_height) {
+            rt_set_last_error("row range exceeds image_height");
+            return RT_ERR_INVALID;
+        }
+    }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (empty) return RT_OK;
+    if (!d_albedo && !d_normal && !d_depth && !d_hits) return RT_OK;  // nothing asked for: no launch
+    if (ctx->n_spheres == 0) { rt_set_last_error("no scene uploaded"); return RT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    if (!rc && !ctx->d_ctr) {
+        size_t cb = 0;
+        rc = ensure_buffer(ctx, (void**)&ctx->d_ctr, &cb, rtk::kCtrBytes);
+        if (!rc) HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrBytes, s));  // as render_rows: on the launch stream
+    }
+    if (rc) return rc;
+    const bool bvh = use_bvh(ctx);
+    const uint64_t P = (uint64_t)n_rows * cam->image_width;
+    rtk::KernelParams p = make_params(cam, row0, row_step, n_rows, ctx->n_spheres);
+    p.s_begin = sample_begin;
+    p.s_count = sample_count;
+    rtk::FeatureArgs fa{};
+    fa.albedo = (double*)d_albedo;
+    fa.normal = (double*)d_normal;
+    fa.depth = (double*)d_depth;
+    fa.hits = d_hits;
+    fa.ctr = ctx->d_ctr;
+    fa.P = (uint32_t)P;
+    if (ctx->timing) {
+        if (ctx->log_used + 1 > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
+        ctx->call_first = ctx->log_used;
+        ctx->log_used += 1;
+        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
+            hipEvent_t e;
+            HIP_CHECK(make_event(&e, true));
+            ctx->events.push_back(e);
+        }
+        ctx->timed_calls = 1;
+    }
+    // the tree and the scene are read-only here, but `launched` / `done` are re-recorded below: a
+    // previous render on another stream is waited for first, so the events still cover it
+    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
+    hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
+    if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+    HIP_CHECK(rtk_launch_features(&p, bvh ? &ctx->bvh : nullptr, ctx->d_geo, ctx->d_mat, &fa, s, &ctx->last_kernel));
+    if (ev) {  // the pass is the sample kernel; there is no reduce pass (an empty interval)
+        HIP_CHECK(hipEventRecord(ev[1], s));
+        HIP_CHECK(hipEventRecord(ev[2], s));
+        HIP_CHECK(hipEventRecord(ev[3], s));
+    }
+    HIP_CHECK(hipEventRecord(ctx->launched, s));
+    ctx->launched_valid = true;
+    ctx->launched_stream = s;
+    HIP_CHECK(hipEventRecord(ctx->done, s));
+    ctx->done_valid = true;
+    return RT_OK;
+}
+
 // ---- adaptive sampling (rt.h) ---------------------------------------------------
 // A gather pass: direct mode over the listed pixels, in as many sub-passes as the sample buffer's cap
 // asks for.  Every sub-pass is a gather sample kernel (which reads each pixel's count for its stream

@@ -7,7 +7,7 @@ from .abi import (RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RT_OUT_LINEAR_F64, RT_
                   RtCamera, RtCameraParams, RtOptions, RtSphere)
 from .api import (PPM, Camera, CameraBuilder, DeviceRenderer, Scene, chapter9_camera,
                   chapter13_camera, encode_p3, encode_p6, final_scene_camera, release_cached_contexts, render,
-                  render_adaptive, render_progressive, sample_key, to_rgb8)
+                  render_adaptive, render_features, render_progressive, sample_key, to_rgb8)
 from .lib import EXPORTED, LIB_PATH, RtError, load
 
 __all__ = [
@@ -15,6 +15,6 @@ __all__ = [
     "RtCamera", "RtCameraParams", "RtOptions", "RtSphere",
     "PPM", "Camera", "CameraBuilder", "DeviceRenderer", "Scene", "chapter9_camera",
     "chapter13_camera", "encode_p3", "encode_p6", "final_scene_camera", "release_cached_contexts", "render",
-    "render_adaptive", "render_progressive", "sample_key", "to_rgb8",
+    "render_adaptive", "render_features", "render_progressive", "sample_key", "to_rgb8",
     "EXPORTED", "LIB_PATH", "RtError", "load",
 ]

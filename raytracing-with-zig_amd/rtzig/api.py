@@ -162,6 +162,11 @@ class Camera:
                                       device=device, output=output, precision=precision, on_round=on_round)
         return PPM(self.width, self.height, img), counts
 
+    def render_features(self, spp, device=0):
+        """The dict of render_features: first-hit albedo, normal, depth, coverage and hits per pixel
+        at `spp` samples; samplesPerPixel of the camera is not used."""
+        return render_features(self.cam, self.scene.world, spp, device=device)
+
 
 _PRECISION = {"f64": abi.RT_PRECISION_F64, "f32": abi.RT_PRECISION_F32}
 
@@ -311,6 +316,48 @@ def render_adaptive(cam, spheres, min_spp, max_spp, step, tolerance, floor=0.01,
         r.close()
 
 
+def render_features(cam, spheres, spp, device=0):
+    """Feature buffers of the whole image on one GPU (rt_render_rows_features at `spp` samples): a dict
+    of numpy arrays for a denoiser or compositor —
+        albedo   (H, W, 3) f64  first-hit albedo, the sums resolved with rt_accum_resolve at spp
+        normal   (H, W, 3) f64  shading normal, likewise (not renormalised)
+        depth    (H, W)    f64  depth_sum / hits, inf where no sample hit
+        coverage (H, W)    f64  hits / spp
+        hits     (H, W)    u32  samples whose camera ray hit a sphere
+    Samples that miss contribute nothing to albedo and normal.  cam.samples_per_pixel is not used."""
+    spp = int(spp)
+    if spp < 1 or spp >= 2 ** 32:
+        raise ValueError("spp must be in [1, 2^32)")
+    import torch
+
+    W, H = cam.image_width, cam.image_height
+    n = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * n)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            sums = torch.empty((2, H * W, 3), dtype=torch.float64, device=dev)  # albedo, normal
+            depth = torch.empty(H * W, dtype=torch.float64, device=dev)
+            hits = torch.empty(H * W, dtype=torch.int32, device=dev)  # u32 on the device
+            out = torch.empty((2, H, W, 3), dtype=torch.float64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            r.features(cam, 0, spp, sums[0].data_ptr(), sums[1].data_ptr(), depth.data_ptr(), hits.data_ptr(),
+                       stream_ptr=stream)
+            r.resolve(sums[0].data_ptr(), H * W, spp, out[0].data_ptr(), stream_ptr=stream)
+            r.resolve(sums[1].data_ptr(), H * W, spp, out[1].data_ptr(), stream_ptr=stream)
+            res = out.cpu().numpy()  # waits for the stream
+            dsum = depth.cpu().numpy().reshape(H, W)
+            cnt = hits.cpu().numpy().view(np.uint32).reshape(H, W)
+            r.sync()  # reports a failure the kernel recorded
+    finally:
+        r.close()
+    mean_depth = np.full((H, W), np.inf)
+    np.divide(dsum, cnt, out=mean_depth, where=cnt != 0)
+    return {"albedo": res[0], "normal": res[1], "depth": mean_depth, "coverage": cnt / float(spp), "hits": cnt}
+
+
 class DeviceRenderer:
     """Device-resident renderer for one GPU (rt_context): scene uploaded once, rows rendered into
     device memory (e.g. a torch tensor's data_ptr) on a caller-provided HIP stream."""
@@ -373,6 +420,22 @@ class DeviceRenderer:
         check("rt_accum_resolve",
               self.lib.rt_accum_resolve(self.ctx, C.c_void_p(d_accum_ptr or 0), n_pixels, n_samples, fmt,
                                         C.c_void_p(d_out_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def features(self, cam, sample_begin, sample_count, d_albedo_ptr=None, d_normal_ptr=None, d_depth_ptr=None,
+                 d_hits_ptr=None, row0=0, row_step=1, n_rows=None, stream_ptr=None):
+        """rt_render_rows_features: the first hit of the camera rays of samples [sample_begin,
+        sample_begin + sample_count), added in sample order to the unscaled per-pixel sums on the device:
+        albedo and normal (n_rows * W x 3 f64 each), depth (n_rows * W f64), hits (n_rows * W u32).  A
+        pointer left None skips that buffer.  sample_begin == 0 starts a new image (the buffers need not
+        be initialised); any split of [0, n) into consecutive passes leaves the bits of one pass.  Always
+        parity arithmetic, whatever set_precision says."""
+        if n_rows is None:
+            n_rows = (cam.image_height - row0 + row_step - 1) // row_step
+        check("rt_render_rows_features",
+              self.lib.rt_render_rows_features(self.ctx, C.byref(cam), row0, row_step, n_rows, sample_begin,
+                                               sample_count, C.c_void_p(d_albedo_ptr or 0),
+                                               C.c_void_p(d_normal_ptr or 0), C.c_void_p(d_depth_ptr or 0),
+                                               C.c_void_p(d_hits_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
     def _pixel_list(self, cam, pixels, n_pixels):
         """(device pointer, length) of a pixel list for accumulate_pixels.  None: every pixel.  An int is

@@ -25,6 +25,7 @@ EXPORTED = [
     "rt_render_pixels_accumulate",
     "rt_accum_select",
     "rt_accum_resolve_counts",
+    "rt_render_rows_features",
     "rt_context_flush",
     "rt_context_fold_pending",
     "rt_kernel_name",
@@ -83,6 +84,8 @@ def _declare(lib):
         "rt_accum_select": (C.c_int, [vp, vp, vp, vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
                                       vp, vp, vp, vp]),
         "rt_accum_resolve_counts": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
+        "rt_render_rows_features": (C.c_int, [vp, P(RtCamera), C.c_uint32, C.c_uint32, C.c_uint32,
+                                              C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
         "rt_context_flush": (C.c_int, [vp]),
         "rt_context_fold_pending": (C.c_int, [vp, P(C.c_int)]),
         "rt_kernel_name": (C.c_char_p, [vp]),

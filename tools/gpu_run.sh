@@ -27,7 +27,11 @@
 #              select / resolve, one render_adaptive run (tools/adaptive_cost.py; its JSON on stdout is
 #              kept as profiles/adaptive/cost.json).  Its GPU tests (tests/test_gpu_adaptive.py) run
 #              with the `tests` step
-#   peak       event-timed VALU peak and issue-cost table (tools/bin/peak_rates, built beforehand)
+#   features   what a feature pass costs: rt_render_rows_features at 16 samples against a bounce_max = 1
+#              colour pass on the same rays, on config 4's image and the 400x225 chapter-13 image
+#              (tools/feature_cost.py; its JSON on stdout is kept as profiles/features/cost.json).  Its
+#              GPU tests (tests/test_gpu_features.py) run with the `tests` step
+#   peak      event-timed VALU peak and issue-cost table (tools/bin/peak_rates, built beforehand)
 #   diag       bounds-checked builds through tools/diag_modes.py (ab/bounds*.so)
 #   uselib     copy $LIB (an ab/*.so build) over the in-tree librtzig.so for the steps after it (on the
 #              box's copy of the tree only)                                     [LIB]
@@ -62,6 +66,7 @@ for step in "$@"; do
     dropin)  run dropin 300 python3 -u tools/dropin_cold.py --runs 3 --configs ${DROPIN_CONFIGS:-2,4,5} ;;
     progressive) run progressive 200 python3 -u tools/progressive_cost.py ;;
     adaptive) run adaptive 300 python3 -u tools/adaptive_cost.py ;;
+    features) run features 200 python3 -u tools/feature_cost.py ;;
     peak)    run peak 300 ./tools/bin/peak_rates ${PEAK_MS:-60} ${PEAK_MODE:-2} ;;
     diag)    run diag 300 python3 -u tools/diag_modes.py raytracing-with-zig_amd/librtzig.so ab/bounds.so --oracle-row ;;
     uselib)  cp "$LIB" raytracing-with-zig_amd/librtzig.so || exit 2; echo "== using $LIB" ;;
