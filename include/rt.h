@@ -318,6 +318,73 @@ int rt_render_rows_features(rt_context* ctx, const rt_camera* cam,
                             uint32_t sample_begin, uint32_t sample_count,
                             void* d_albedo, void* d_normal, void* d_depth, uint32_t* d_hits,
                             void* stream);
+/* ---- denoise: a variance- and feature-guided à-trous filter, bit-exact to its spec
+ * Turns the buffers of an every-pixel gather pass (rt_render_pixels_accumulate with a NULL list: the
+ * unscaled colour sums, the squared-luminance sums m2, the counts) and of a feature pass over all rows
+ * (rt_render_rows_features) into a clean image.  Every operation below is IEEE f64, correctly rounded,
+ * with no fused multiply-add and no transcendental function, in exactly this order, so the result
+ * depends on nothing but the buffers and the parameters — not on tile shape, launch shape or which
+ * kernel form ran a level.  P = W*H, pixel p = j*W + i.
+ *
+ * Prepare, per pixel, n = (double)counts[p]:
+ *   colour    c_k = accum[p][k] * (1.0 / n), 0 when counts[p] == 0 (rt_accum_resolve_counts' bits);
+ *   variance  of the mean luminance: S = (a0 + a1) + a2; mean = S / n; v = m2[p] - S * mean;
+ *             var = v > 0 ? (v / (n - 1)) / n : 0; var = 0 when counts[p] < 2;
+ *   guides    fi = 1.0 / (double)feature_samples: A_k = albedo[p][k] * fi; N_k = normal[p][k] * fi (not
+ *             renormalised); h = (double)hits[p]; cov = h * fi; z = hits[p] ? depth[p] / h : 0.
+ *             A guide whose pointer is NULL is 0 everywhere: its term vanishes.
+ * Variance prefilter, once: 3x3, taps ty = -1..1 outer, tx = -1..1 inner, only taps inside the image:
+ *   g = G[ty] * G[tx], G = {0.25, 0.5, 0.25}; sv += g * var_q; sg += g; then v0 = sv / sg.
+ * Level k = 0 .. levels - 1, step s = 2^k, reads (c, v) of the previous level and writes (c', v'):
+ *   l_p = (c0 + c1) + c2 (likewise l_q); isd = 1.0 / (sigma_l * sqrt(v_p) + epsilon);
+ *   sw = 0; sc[3] = 0; sv = 0;
+ *   for ty = -2..2 (outer), tx = -2..2 (inner), q = (i + tx*s, j + ty*s), skipped outside the image:
+ *     dl = |l_p - l_q| * isd
+ *     dn = sigma_n * (((Np0-Nq0)^2 + (Np1-Nq1)^2) + (Np2-Nq2)^2)          x^2 is x * x
+ *     da = sigma_a * (((Ap0-Aq0)^2 + (Ap1-Aq1)^2) + (Ap2-Aq2)^2)
+ *     dh = sigma_h * |cov_p - cov_q|
+ *     r  = (double)(max(|tx|, |ty|) * s)
+ *     dz = (r > 0 && z_p > 0 && z_q > 0) ? |z_p - z_q| / ((sigma_z * r) * (z_p + z_q) + epsilon) : 0
+ *     d  = ((dl + dn) + da) + (dh + dz)
+ *     x  = 1.0 - d * 0.125; t = x > 0 ? x : 0; t = t*t; t = t*t; t = t*t     (1 - d/8)^8 for exp(-d)
+ *     w  = t * (K[ty] * K[tx]), K = {1, 4, 6, 4, 1} / 16 (the product is exact)
+ *     sw += w; sc_k += w * c_q,k; sv += (w * w) * v_q
+ *   rs = 1.0 / sw; c'_k = sc_k * rs; v' = sv * (rs * rs)
+ * The centre tap has d = 0, so sw >= 36/256.  d_out receives the last level's c, linear f64 (3 doubles
+ * per pixel) or the fused Color.toRgb (3 bytes); d_var_out (P doubles, may be NULL) the last level's v.
+ * levels == 0: the prepared colour and the prefiltered variance.
+ *
+ * params == NULL: rt_denoise_default_params' values (levels 2, sigma_l 4, sigma_n 32, sigma_a 32,
+ * sigma_z 0.05, sigma_h 4, epsilon 1e-6).  Finite sums are a caller contract: with a NaN or infinite
+ * input the output is unspecified, but the call neither faults nor hangs.  The inputs are not
+ * modified; d_out and d_var_out must not alias them.
+ *
+ * Launch: asynchronous on `stream`; a plain one-stream call (a pending deferred reduce pass runs
+ * first): a prepare pass, the prefilter and one kernel per level.  Workspace: 128 B per pixel, held by
+ * the context (rt_context_workspace_bytes counts it; the 25% give-back rule applies).
+ * rt_context_kernel_times reports the whole call as sample_ms, with reduce_ms 0.  Instrumented
+ * contexts are accepted; the call writes no stats.
+ * RT_ERR_INVALID, each answered before any device is touched: null ctx, d_accum, d_m2, d_counts or
+ * d_out; width or height 0, or W*H >= 2^32; d_depth without d_hits; a guide pointer with
+ * feature_samples == 0; levels > 16; a sigma that is negative or NaN; epsilon not > 0;
+ * reserved != 0; a bad output_format. */
+typedef struct rt_denoise_params {
+    uint32_t levels;     /* à-trous levels, step 2^k at level k; at most 16 */
+    uint32_t reserved;   /* must be 0 */
+    double sigma_l;      /* luminance, in standard deviations of the pixel's mean */
+    double sigma_n;      /* squared normal distance */
+    double sigma_a;      /* squared albedo distance */
+    double sigma_z;      /* relative depth difference per pixel of tap distance */
+    double sigma_h;      /* coverage difference */
+    double epsilon;      /* added to both denominators; > 0 */
+} rt_denoise_params;     /* 56 bytes */
+int rt_denoise_default_params(rt_denoise_params* out);
+int rt_denoise(rt_context* ctx, uint32_t width, uint32_t height,
+               const void* d_accum, const void* d_m2, const uint32_t* d_counts,
+               const void* d_albedo, const void* d_normal, const void* d_depth,
+               const uint32_t* d_hits, uint32_t feature_samples,
+               const rt_denoise_params* params, uint32_t output_format,
+               void* d_out, void* d_var_out, void* stream);
 /* Runs a pending deferred reduce pass (on the out_stream of the call that deferred it); no-op otherwise. */
 int rt_context_flush(rt_context* ctx);
 /* *pending = 1 if the last deferred call left its output pending (direct mode), else 0. */
@@ -337,7 +404,7 @@ const char* rt_kernel_name(rt_context* ctx);
  * same bits as any tree, fewer node visits)}. */
 int rt_context_tree_info(rt_context* ctx, uint32_t* info);
 /* Device bytes the context's render workspace holds now (rings, sums, flags, direct-mode samples,
- * schedule, counters, rt_accum_select's scratch; not the scene or caller buffers): see rt_render
+ * schedule, counters, rt_accum_select's scratch, rt_denoise's planes; not the scene or caller buffers): see rt_render
  * "Workspace". */
 int rt_context_workspace_bytes(rt_context* ctx, uint64_t* bytes);
 /* Optional kernel timing with HIP events recorded on the launch stream around the kernels of every

@@ -37,6 +37,7 @@
 
 #include "../../include/rt.h"
 #include "rt_bvh.hpp"
+#include "rt_denoise.h"
 #include "rt_device.h"
 #include "rt_kernel.h"
 #include "rt_schedule.hpp"
@@ -158,6 +159,8 @@ struct rt_context {
     unsigned long long* d_ctr = nullptr;  // rtk::kCtrBytes, zeroed per launch ([kErrWord]: error word)
     void* d_select = nullptr;       // rt_accum_select's scratch: block counts + wave ballots (rt_kernel.h)
     size_t select_bytes = 0;
+    void* d_denoise = nullptr;      // rt_denoise's planes: guides, two colour + variance buffers (rt_denoise.h)
+    size_t denoise_bytes = 0;
     const char* last_kernel = "sample_kernel";
     SceneData scene;                // host copy (BVH rebuilds for far-away cameras, scene comparisons)
     rtk::BvhArgs bvh{};
@@ -769,7 +772,7 @@ int rt_context_destroy(rt_context* ctx) {
         (void)hipDeviceSynchronize();
     }
     for (void* p : {(void*)ctx->d_geo, (void*)ctx->d_mat, (void*)ctx->d_ring, (void*)ctx->d_sums, (void*)ctx->d_flags,
-                    (void*)ctx->d_samples, (void*)ctx->d_samples2, (void*)ctx->d_fold_ctr, (void*)ctx->d_sched, (void*)ctx->d_sched_acc, (void*)ctx->d_ctr, ctx->d_select, (void*)ctx->d_nodes, (void*)ctx->d_leaves, (void*)ctx->d_always_geo,
+                    (void*)ctx->d_samples, (void*)ctx->d_samples2, (void*)ctx->d_fold_ctr, (void*)ctx->d_sched, (void*)ctx->d_sched_acc, (void*)ctx->d_ctr, ctx->d_select, ctx->d_denoise, (void*)ctx->d_nodes, (void*)ctx->d_leaves, (void*)ctx->d_always_geo,
                     (void*)ctx->d_always_sid, ctx->d_out, (void*)ctx->d_stats})
         (void)hipFree(p);
     if (ctx->h_out) (void)hipHostFree(ctx->h_out);
@@ -1432,6 +1435,125 @@ int rt_accum_resolve_counts(rt_context* ctx, const void* d_accum, const uint32_t
     return RT_OK;
 }
 
+// ---- denoise (rt.h) --------------------------------------------------------------
+int rt_denoise_default_params(rt_denoise_params* out) {
+    if (!out) { rt_set_last_error("null params output"); return RT_ERR_INVALID; }
+    out->levels = 2;  // the best RMSE on config 4's image (profiles/denoise/quality.json)
+    out->reserved = 0;
+    out->sigma_l = 4.0;
+    out->sigma_n = 32.0;
+    out->sigma_a = 32.0;
+    out->sigma_z = 0.05;
+    out->sigma_h = 4.0;
+    out->epsilon = 1e-6;
+    return RT_OK;
+}
+
+// The prepare pass, the variance prefilter and one launch per level, all on `stream`; the planes live
+// in the context's workspace and the last pass writes the caller's buffers.
+int rt_denoise(rt_context* ctx, uint32_t width, uint32_t height, const void* d_accum, const void* d_m2,
+               const uint32_t* d_counts, const void* d_albedo, const void* d_normal, const void* d_depth,
+               const uint32_t* d_hits, uint32_t feature_samples, const rt_denoise_params* params, uint32_t output_format,
+               void* d_out, void* d_var_out, void* stream) {
+    // the argument checks that need no context come first, the context last: each answers before
+    // anything touches a device
+    if (!d_accum) { rt_set_last_error("null accumulator"); return RT_ERR_INVALID; }
+    if (!d_m2) { rt_set_last_error("null m2"); return RT_ERR_INVALID; }
+    if (!d_counts) { rt_set_last_error("null counts"); return RT_ERR_INVALID; }
+    if (!d_out) { rt_set_last_error("null output"); return RT_ERR_INVALID; }
+    if (width == 0 || height == 0) { rt_set_last_error("width and height must be > 0"); return RT_ERR_INVALID; }
+    const uint64_t P = (uint64_t)width * height;
+    if (P >= (1ull << 32)) { rt_set_last_error("width * height must be below 2^32"); return RT_ERR_INVALID; }
+    if (d_depth && !d_hits) { rt_set_last_error("depth needs hits (mean depth is depth / hits)"); return RT_ERR_INVALID; }
+    if ((d_albedo || d_normal || d_depth || d_hits) && feature_samples == 0) {
+        rt_set_last_error("feature_samples must be > 0 when a guide buffer is given");
+        return RT_ERR_INVALID;
+    }
+    rt_denoise_params prm;
+    rt_denoise_default_params(&prm);
+    if (params) prm = *params;
+    if (prm.levels > rtk::kDenoiseMaxLevels) { rt_set_last_error("levels must be at most 16"); return RT_ERR_INVALID; }
+    const std::pair<const char*, double> sigmas[] = {{"sigma_l", prm.sigma_l}, {"sigma_n", prm.sigma_n},
+                                                     {"sigma_a", prm.sigma_a}, {"sigma_z", prm.sigma_z},
+                                                     {"sigma_h", prm.sigma_h}};
+    for (const auto& sg : sigmas)
+        if (!(sg.second >= 0)) {
+            rt_set_last_error(std::string(sg.first) + " must be a number >= 0");
+            return RT_ERR_INVALID;
+        }
+    if (!(prm.epsilon > 0)) { rt_set_last_error("epsilon must be > 0"); return RT_ERR_INVALID; }
+    if (prm.reserved != 0) { rt_set_last_error("reserved must be 0"); return RT_ERR_INVALID; }
+    if (output_format > RT_OUT_RGB8) { rt_set_last_error("bad output_format"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    if (!rc) rc = fit_buffer(ctx, &ctx->d_denoise, &ctx->denoise_bytes, (size_t)P * rtk::kDenoiseBytesPerPixel);
+    if (rc) return rc;
+    // test hook RTZIG_DENOISE_FORM=tile|direct (read per call) forces the level kernel's form; a step
+    // whose tile grid does not fit a launch runs the direct form either way.  Same bits.
+    int force = 0;
+    if (const char* e = std::getenv("RTZIG_DENOISE_FORM")) force = std::strcmp(e, "tile") == 0 ? 1 : std::strcmp(e, "direct") == 0 ? 2 : 0;
+    double* g = (double*)ctx->d_denoise;  // [P][8], then the two [P][4] planes
+    double* cv[2] = {g + 8 * (size_t)P, g + 12 * (size_t)P};
+    if (ctx->timing) {
+        if (ctx->log_used + 1 > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
+        ctx->call_first = ctx->log_used;
+        ctx->log_used += 1;
+        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
+            hipEvent_t e;
+            HIP_CHECK(make_event(&e, true));
+            ctx->events.push_back(e);
+        }
+        ctx->timed_calls = 1;
+    }
+    // the planes belong to the context: a previous call on another stream is waited for first
+    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
+    hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
+    if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+    rtk::DenoisePrepareArgs pa{};
+    pa.accum = (const double*)d_accum;
+    pa.m2 = (const double*)d_m2;
+    pa.counts = d_counts;
+    pa.albedo = (const double*)d_albedo;
+    pa.normal = (const double*)d_normal;
+    pa.depth = (const double*)d_depth;
+    pa.hits = d_hits;
+    pa.fi = feature_samples ? 1.0 / (double)feature_samples : 0.0;
+    pa.cv = cv[0];
+    pa.g = g;
+    pa.P = (uint32_t)P;
+    HIP_CHECK(rtk_launch_denoise_prepare(&pa, s));
+    const rtk::DenoiseSink last{nullptr, d_out, (double*)d_var_out, output_format};
+    const rtk::DenoiseSink pre = prm.levels == 0 ? last : rtk::DenoiseSink{cv[1], nullptr, nullptr, 0};
+    HIP_CHECK(rtk_launch_denoise_prefilter(cv[0], width, height, &pre, s));
+    for (uint32_t k = 0; k < prm.levels; k++) {  // level k reads cv[(k + 1) & 1] and writes cv[k & 1]
+        rtk::DenoiseLevelArgs la{};
+        la.cv = cv[(k + 1) & 1];
+        la.g = g;
+        la.sink = k + 1 == prm.levels ? last : rtk::DenoiseSink{cv[k & 1], nullptr, nullptr, 0};
+        la.p = rtk::DenoiseParams{prm.sigma_l, prm.sigma_n, prm.sigma_a, prm.sigma_z, prm.sigma_h, prm.epsilon};
+        la.W = width;
+        la.H = height;
+        la.step = 1u << k;
+        const bool tile = (force == 1 || (force == 0 && la.step <= rtk::kDnTileMaxStep)) &&
+                          rtk_denoise_tile_ok(width, height, la.step);
+        HIP_CHECK(rtk_launch_denoise_level(&la, tile ? 1 : 0, s));
+    }
+    if (ev) {  // the call is reported as the sample kernel; there is no reduce pass (an empty interval)
+        HIP_CHECK(hipEventRecord(ev[1], s));
+        HIP_CHECK(hipEventRecord(ev[2], s));
+        HIP_CHECK(hipEventRecord(ev[3], s));
+    }
+    HIP_CHECK(hipEventRecord(ctx->launched, s));
+    ctx->launched_valid = true;
+    ctx->launched_stream = s;
+    HIP_CHECK(hipEventRecord(ctx->done, s));
+    ctx->done_valid = true;
+    ctx->last_kernel = "denoise";
+    return RT_OK;
+}
+
 int rt_context_fold_pending(rt_context* ctx, int* pending) {
     if (!ctx || !pending) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
     *pending = ctx->fold_pending ? 1 : 0;
@@ -1519,7 +1641,7 @@ int rt_context_workspace_bytes(rt_context* ctx, uint64_t* bytes) {
     if (!ctx || !bytes) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
     *bytes = (uint64_t)ctx->ring_bytes + ctx->sums_bytes + ctx->flags_bytes + ctx->samples_bytes + ctx->samples2_bytes +
              ctx->sched_bytes + ctx->sched_acc_bytes + (ctx->d_fold_ctr ? 2 * 16 * sizeof(unsigned long long) : 0) +
-             (ctx->d_ctr ? rtk::kCtrBytes : 0) + ctx->select_bytes;
+             (ctx->d_ctr ? rtk::kCtrBytes : 0) + ctx->select_bytes + ctx->denoise_bytes;
     return RT_OK;
 }
 

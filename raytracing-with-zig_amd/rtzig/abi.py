@@ -90,6 +90,21 @@ class RtCameraParams(C.Structure):
     ]
 
 
+class RtDenoiseParams(C.Structure):
+    """rt_denoise_params: the à-trous filter's level count and edge-stopping sigmas (rt.h rt_denoise)."""
+    _fields_ = [
+        ("levels", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("sigma_l", C.c_double),
+        ("sigma_n", C.c_double),
+        ("sigma_a", C.c_double),
+        ("sigma_z", C.c_double),
+        ("sigma_h", C.c_double),
+        ("epsilon", C.c_double),
+    ]
+
+
+DENOISE_PARAMS_SIZE = 56
 SPHERE_SIZE = 80
 CAMERA_SIZE = 200
 CAMERA_PARAMS_SIZE = 144

@@ -167,6 +167,13 @@ class Camera:
         at `spp` samples; samplesPerPixel of the camera is not used."""
         return render_features(self.cam, self.scene.world, spp, device=device)
 
+    def render_denoised(self, spp, feature_spp=4, params=None, adaptive=None, device=0, output="linear",
+                        precision="f64"):
+        """The dict of render_denoised: `spp` samples per pixel (more where adaptive= asks for them),
+        `feature_spp` feature samples, then rt_denoise; samplesPerPixel of the camera is not used."""
+        return render_denoised(self.cam, self.scene.world, spp, feature_spp=feature_spp, params=params,
+                               adaptive=adaptive, device=device, output=output, precision=precision)
+
 
 _PRECISION = {"f64": abi.RT_PRECISION_F64, "f32": abi.RT_PRECISION_F32}
 
@@ -258,6 +265,29 @@ def _adaptive_args(min_spp, max_spp, step, tolerance, floor, output):
     return min_spp, max_spp, step, tolerance, floor
 
 
+def _adaptive_rounds(r, cam, accum, m2, counts, lst, n_sel, min_spp, max_spp, step, tolerance, floor, stream,
+                     on_round=None):
+    """render_adaptive's loop on the caller's device tensors (counts zeroed): min_spp samples for every
+    pixel, then rounds of selection and `step` more samples until nothing is selected."""
+    n_pix = counts.numel()
+    r.accumulate_pixels(cam, None, min_spp, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), stream_ptr=stream)
+    rnd = 0
+    while True:
+        r.select(accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), n_pix, min_spp, max_spp, tolerance, floor,
+                 lst.data_ptr(), n_sel.data_ptr(), stream_ptr=stream)
+        k = int(n_sel.item())  # the round's host sync
+        if on_round is not None:
+            on_round(rnd, lst[:k], accum, m2, counts)
+        if k == 0:
+            break
+        # a pixel selected now was selected in every round before: all of the list stand at
+        # min_spp + rnd * step samples, so one clamp keeps every pixel within max_spp
+        more = min(step, max_spp - (min_spp + rnd * step))
+        r.accumulate_pixels(cam, lst.data_ptr(), more, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(),
+                            n_pixels=k, stream_ptr=stream)
+        rnd += 1
+
+
 def render_adaptive(cam, spheres, min_spp, max_spp, step, tolerance, floor=0.01, device=0, output="linear",
                     precision="f64", on_round=None):
     """Adaptive render on one GPU: every pixel gets min_spp samples; then, round after round, the
@@ -291,22 +321,8 @@ def render_adaptive(cam, spheres, min_spp, max_spp, step, tolerance, floor=0.01,
             n_sel = torch.zeros(1, dtype=torch.int32, device=dev)
             out = torch.empty((H, W, 3), dtype=torch.float64 if output == "linear" else torch.uint8, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
-            r.accumulate_pixels(cam, None, min_spp, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), stream_ptr=stream)
-            rnd = 0
-            while True:
-                r.select(accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), H * W, min_spp, max_spp, tolerance, floor,
-                         lst.data_ptr(), n_sel.data_ptr(), stream_ptr=stream)
-                k = int(n_sel.item())  # the round's host sync
-                if on_round is not None:
-                    on_round(rnd, lst[:k], accum, m2, counts)
-                if k == 0:
-                    break
-                # a pixel selected now was selected in every round before: all of the list stand at
-                # min_spp + rnd * step samples, so one clamp keeps every pixel within max_spp
-                more = min(step, max_spp - (min_spp + rnd * step))
-                r.accumulate_pixels(cam, lst.data_ptr(), more, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(),
-                                    n_pixels=k, stream_ptr=stream)
-                rnd += 1
+            _adaptive_rounds(r, cam, accum, m2, counts, lst, n_sel, min_spp, max_spp, step, tolerance, floor, stream,
+                             on_round)
             r.resolve_counts(accum.data_ptr(), counts.data_ptr(), H * W, out.data_ptr(), output=output, stream_ptr=stream)
             img = out.cpu().numpy()  # waits for the stream
             cnt = counts.cpu().numpy().view(np.uint32).reshape(H, W)
@@ -356,6 +372,87 @@ def render_features(cam, spheres, spp, device=0):
     mean_depth = np.full((H, W), np.inf)
     np.divide(dsum, cnt, out=mean_depth, where=cnt != 0)
     return {"albedo": res[0], "normal": res[1], "depth": mean_depth, "coverage": cnt / float(spp), "hits": cnt}
+
+
+def denoise_params(**overrides):
+    """rt_denoise_params: the library's defaults (rt_denoise_default_params: levels 2, sigma_l 4,
+    sigma_n 32, sigma_a 32, sigma_z 0.05, sigma_h 4, epsilon 1e-6) with the given fields replaced."""
+    p = abi.RtDenoiseParams()
+    check("rt_denoise_default_params", load().rt_denoise_default_params(C.byref(p)))
+    names = [n for n, _ in abi.RtDenoiseParams._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError(f"denoise_params: no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def render_denoised(cam, spheres, spp, feature_spp=4, params=None, adaptive=None, device=0, output="linear",
+                    precision="f64"):
+    """A denoised render on one GPU: every pixel gets `spp` samples (a gather pass over every pixel,
+    which also fills the squared-luminance sums); with adaptive=dict(max_spp=, step=, tolerance=,
+    floor=0.01) render_adaptive's rounds then add samples from min_spp = spp; then `feature_spp`
+    feature samples (rt_render_rows_features) and rt_denoise (params: denoise_params(), None for the
+    defaults).  Returns a dict of numpy arrays:
+        image    (H, W, 3)  the denoised image, linear f64 or rgb8 u8
+        noisy    (H, W, 3)  the input image (rt_accum_resolve_counts), same format
+        variance (H, W) f64 the filtered variance of the mean luminance
+        counts   (H, W) u32 the samples each pixel got
+    cam.samples_per_pixel is not used."""
+    if output not in ("linear", "rgb8"):
+        raise ValueError(output)
+    spp, feature_spp = int(spp), int(feature_spp)
+    if spp < 2 or spp >= 2 ** 32:
+        raise ValueError("spp must be in [2, 2^32) (the variance estimate needs two samples)")
+    if feature_spp < 1 or feature_spp >= 2 ** 32:
+        raise ValueError("feature_spp must be in [1, 2^32)")
+    if adaptive is not None:
+        extra = set(adaptive) - {"max_spp", "step", "tolerance", "floor"}
+        if extra or not {"max_spp", "step", "tolerance"} <= set(adaptive):
+            raise ValueError("adaptive: a dict of max_spp, step, tolerance and optionally floor")
+        _, max_spp, step, tolerance, floor = _adaptive_args(spp, adaptive["max_spp"], adaptive["step"],
+                                                            adaptive["tolerance"], adaptive.get("floor", 0.01), output)
+    import torch
+
+    W, H = cam.image_width, cam.image_height
+    n = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * n)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        r.set_precision(precision)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            accum = torch.empty((H * W, 3), dtype=torch.float64, device=dev)
+            m2 = torch.empty(H * W, dtype=torch.float64, device=dev)
+            counts = torch.zeros(H * W, dtype=torch.int32, device=dev)  # u32 on the device
+            sums = torch.empty((2, H * W, 3), dtype=torch.float64, device=dev)  # albedo, normal
+            depth = torch.empty(H * W, dtype=torch.float64, device=dev)
+            hits = torch.empty(H * W, dtype=torch.int32, device=dev)  # u32 on the device
+            odt = torch.float64 if output == "linear" else torch.uint8
+            out = torch.empty((2, H, W, 3), dtype=odt, device=dev)  # denoised, noisy
+            var = torch.empty((H, W), dtype=torch.float64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if adaptive is None:
+                r.accumulate_pixels(cam, None, spp, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), stream_ptr=stream)
+            else:
+                lst = torch.empty(H * W, dtype=torch.int32, device=dev)
+                n_sel = torch.zeros(1, dtype=torch.int32, device=dev)
+                _adaptive_rounds(r, cam, accum, m2, counts, lst, n_sel, spp, max_spp, step, tolerance, floor, stream)
+            r.features(cam, 0, feature_spp, sums[0].data_ptr(), sums[1].data_ptr(), depth.data_ptr(), hits.data_ptr(),
+                       stream_ptr=stream)
+            r.denoise(W, H, accum.data_ptr(), m2.data_ptr(), counts.data_ptr(), out[0].data_ptr(),
+                      d_albedo_ptr=sums[0].data_ptr(), d_normal_ptr=sums[1].data_ptr(), d_depth_ptr=depth.data_ptr(),
+                      d_hits_ptr=hits.data_ptr(), feature_samples=feature_spp, params=params, output=output,
+                      d_var_out_ptr=var.data_ptr(), stream_ptr=stream)
+            r.resolve_counts(accum.data_ptr(), counts.data_ptr(), H * W, out[1].data_ptr(), output=output, stream_ptr=stream)
+            res = out.cpu().numpy()  # waits for the stream
+            v = var.cpu().numpy()
+            cnt = counts.cpu().numpy().view(np.uint32).reshape(H, W)
+            r.sync()  # reports a failure the kernel recorded
+        return {"image": res[0], "noisy": res[1], "variance": v, "counts": cnt}
+    finally:
+        r.close()
 
 
 class DeviceRenderer:
@@ -509,6 +606,24 @@ class DeviceRenderer:
         check("rt_accum_resolve_counts",
               self.lib.rt_accum_resolve_counts(self.ctx, C.c_void_p(d_accum_ptr or 0), C.c_void_p(d_counts_ptr or 0),
                                                n_pixels, fmt, C.c_void_p(d_out_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def denoise(self, width, height, d_accum_ptr, d_m2_ptr, d_counts_ptr, d_out_ptr, d_albedo_ptr=None,
+                d_normal_ptr=None, d_depth_ptr=None, d_hits_ptr=None, feature_samples=0, params=None, output="linear",
+                d_var_out_ptr=None, stream_ptr=None):
+        """rt_denoise: the variance- and feature-guided à-trous filter over whole-image device buffers —
+        the colour sums, squared-luminance sums and counts of accumulate_pixels, guided by the sums of
+        features() at `feature_samples` samples (a pointer left None: that guide is 0) — into d_out
+        (width * height x 3, linear f64 or rgb8) and, optionally, the filtered variance of the mean
+        luminance into d_var_out (width * height f64).  params: denoise_params(), None for the defaults.
+        The inputs are not modified; asynchronous."""
+        fmt = abi.RT_OUT_LINEAR_F64 if output == "linear" else abi.RT_OUT_RGB8
+        check("rt_denoise",
+              self.lib.rt_denoise(self.ctx, width, height, C.c_void_p(d_accum_ptr or 0), C.c_void_p(d_m2_ptr or 0),
+                                  C.c_void_p(d_counts_ptr or 0), C.c_void_p(d_albedo_ptr or 0),
+                                  C.c_void_p(d_normal_ptr or 0), C.c_void_p(d_depth_ptr or 0),
+                                  C.c_void_p(d_hits_ptr or 0), feature_samples,
+                                  C.byref(params) if params is not None else None, fmt, C.c_void_p(d_out_ptr or 0),
+                                  C.c_void_p(d_var_out_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
     def flush(self):
         """Runs a pending deferred reduce pass (rt_context_flush)."""

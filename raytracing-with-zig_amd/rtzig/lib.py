@@ -6,7 +6,7 @@ render call goes through the HIP kernel on a gfx950 device (rt_render / rt_rende
 import ctypes as C
 import os
 
-from .abi import RtCamera, RtCameraParams, RtOptions, RtSphere
+from .abi import RtCamera, RtCameraParams, RtDenoiseParams, RtOptions, RtSphere
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "librtzig.so")
@@ -26,6 +26,8 @@ EXPORTED = [
     "rt_accum_select",
     "rt_accum_resolve_counts",
     "rt_render_rows_features",
+    "rt_denoise_default_params",
+    "rt_denoise",
     "rt_context_flush",
     "rt_context_fold_pending",
     "rt_kernel_name",
@@ -86,6 +88,9 @@ def _declare(lib):
         "rt_accum_resolve_counts": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_uint32, vp, vp]),
         "rt_render_rows_features": (C.c_int, [vp, P(RtCamera), C.c_uint32, C.c_uint32, C.c_uint32,
                                               C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]),
+        "rt_denoise_default_params": (C.c_int, [P(RtDenoiseParams)]),
+        "rt_denoise": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32,
+                                 P(RtDenoiseParams), C.c_uint32, vp, vp, vp]),
         "rt_context_flush": (C.c_int, [vp]),
         "rt_context_fold_pending": (C.c_int, [vp, P(C.c_int)]),
         "rt_kernel_name": (C.c_char_p, [vp]),

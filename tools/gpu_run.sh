@@ -31,6 +31,11 @@
 #              colour pass on the same rays, on config 4's image and the 400x225 chapter-13 image
 #              (tools/feature_cost.py; its JSON on stdout is kept as profiles/features/cost.json).  Its
 #              GPU tests (tests/test_gpu_features.py) run with the `tests` step
+#   denoise   what rt_denoise costs against the 16-sample gather pass it stands in for, per level and
+#              kernel form, and the RMSE table against a 500-spp frame, on config 4's image
+#              (tools/denoise_cost.py; the "cost" and "quality" objects of its JSON on stdout are kept
+#              as profiles/denoise/cost.json and quality.json).  Its GPU
+#              tests (tests/test_gpu_denoise.py) run with the `tests` step
 #   peak      event-timed VALU peak and issue-cost table (tools/bin/peak_rates, built beforehand)
 #   diag       bounds-checked builds through tools/diag_modes.py (ab/bounds*.so)
 #   uselib     copy $LIB (an ab/*.so build) over the in-tree librtzig.so for the steps after it (on the
@@ -67,6 +72,7 @@ for step in "$@"; do
     progressive) run progressive 200 python3 -u tools/progressive_cost.py ;;
     adaptive) run adaptive 300 python3 -u tools/adaptive_cost.py ;;
     features) run features 200 python3 -u tools/feature_cost.py ;;
+    denoise) run denoise 300 python3 -u tools/denoise_cost.py ;;
     peak)    run peak 300 ./tools/bin/peak_rates ${PEAK_MS:-60} ${PEAK_MODE:-2} ;;
     diag)    run diag 300 python3 -u tools/diag_modes.py raytracing-with-zig_amd/librtzig.so ab/bounds.so --oracle-row ;;
     uselib)  cp "$LIB" raytracing-with-zig_amd/librtzig.so || exit 2; echo "== using $LIB" ;;
