@@ -385,6 +385,94 @@ int rt_denoise(rt_context* ctx, uint32_t width, uint32_t height,
                const uint32_t* d_hits, uint32_t feature_samples,
                const rt_denoise_params* params, uint32_t output_format,
                void* d_out, void* d_var_out, void* stream);
+/* ---- temporal accumulation: the previous frame's sums reprojected into the next ---
+ * For a static scene seen by a moving camera.  `prev` holds the previous frame's buffers — the unscaled
+ * colour sums, m2 and counts of an every-pixel gather pass (rt_render_pixels_accumulate, NULL list) and
+ * the sums of a feature pass over all rows (rt_render_rows_features) at prev->feature_samples samples,
+ * rendered with cam_prev — and `cur` the current frame's, freshly rendered with cam.  For every pixel the
+ * call finds where the pixel's first-hit point was in the previous image, checks that the previous image
+ * saw the same surface there, and if so adds the previous frame's per-sample means to the current sums
+ * as nh pseudo-samples.  The merged (accum, m2, counts) are at once rt_denoise's input and the next
+ * frame's history: there is no separate history format.  Only the first frame of a sequence is
+ * bit-identical to a one-pass render at its counts; a merged pixel's sums are an estimate that mixes
+ * two frames, and rt_accum_resolve_counts gives its blended mean.
+ *
+ * Every operation below is IEEE f64, correctly rounded, with no fused multiply-add and no
+ * transcendental function, in exactly this order; every comparison is written so that a NaN makes it
+ * false.  dot(x,y) = (x0*y0 + x1*y1) + x2*y2; cross(a,b) = (a1*b2 - a2*b1, a2*b0 - a0*b2,
+ * a0*b1 - a1*b0); x^2 is x*x.  Primed names belong to cam_prev / prev.  P = W*H, pixel p = j*W + i.
+ *
+ * Per call, from cam_prev:  A = pixel0' - center';  n = cross(du', dv');  an = dot(A, n);
+ *   nn = dot(n, n);  rnn = 1.0 / nn.
+ * Per pixel p = (i, j), c = counts[p], h = hits[p]:
+ *  1. h == 0: no history (the sky is an analytic function of the ray; there is no point to reproject).
+ *  2. The first-hit point.  z = depth[p] / (double)h;
+ *     D_k = ((pixel0_k + du_k*(double)i) + dv_k*(double)j) - center_k   (getRay's order, camera.zig:189,198,
+ *     with a zero offset; pixel centres lie at integer coordinates, camera.zig:318);
+ *     L = sqrt(dot(D,D));  g = z / L;  X_k = center_k + D_k*g.
+ *  3. Its place in the previous image.  E = X - center';  en = dot(E,n);  s = an / en; the point lies in
+ *     front of the previous camera iff s > 0 && s < +inf, else no history.  Q_k = s*E_k - A_k;
+ *     u = dot(cross(Q, dv'), n) * rnn;  v = dot(cross(du', Q), n) * rnn;  r = sqrt(dot(E,E)).
+ *  4. The taps.  fu = floor(u), fv = floor(v); in range iff fu >= -1 && fu <= W-1 && fv >= -1 &&
+ *     fv <= H-1, else no history; only then are they converted to integers i0, j0.  fx = u - fu, fy = v - fv.
+ *  5. For b = 0,1 (outer), a = 0,1 (inner): q = (i0+a, j0+b), skipped outside the image;
+ *     bw = (a ? fx : 1.0 - fx) * (b ? fy : 1.0 - fy); the tap is skipped when bw == 0.  It is VALID iff
+ *       counts'[q] > 0 && hits'[q] > 0;
+ *       |z_q - r| <= sigma_z * r, with z_q = depth'[q] / (double)hits'[q];
+ *       dn <= tau_n, dn = ((Np0-Nq0)^2 + (Np1-Nq1)^2) + (Np2-Nq2)^2, N = normal * fi,
+ *         fi = 1.0 / (double)feature_samples (each frame its own);
+ *       da <= tau_a, the same on albedo;
+ *       |cov_p - cov_q| <= tau_h, cov = (double)hits * fi.
+ *     A guide that is NULL contributes no test.  A valid tap adds, with rn = 1.0 / (double)counts'[q]:
+ *       sw += bw;  sc_k += bw * (accum'[q][k] * rn);  sq += bw * (m2'[q] * rn);  nmin = min(nmin, counts'[q]).
+ *  6. History is taken iff at least one tap was valid and sw >= min_weight.  Then
+ *     nh = min(nmin, max_history, 2^32 - 1 - c); nh == 0: no history.  rs = 1.0 / sw; hd = (double)nh;
+ *       accum[p][k] = (c ? accum[p][k] : 0) + (sc_k*rs)*hd;   m2[p] = (c ? m2[p] : 0) + (sq*rs)*hd;
+ *       counts[p] = c + nh;   d_history[p] = nh.
+ *     Without history d_history[p] = 0 and no byte of `cur` at that pixel is written.  A pixel with
+ *     c == 0 starts from 0: its accum and m2 entries are not read.
+ * m2 is a sum of squared sample luminances, and the history's mean second moment times nh is the same
+ * kind of quantity: the variance estimates of rt_accum_select and rt_denoise keep their meaning on merged
+ * buffers.  In the steady state a pixel carries n + max_history samples, so max_history is the blend
+ * factor: alpha = n / (n + max_history).
+ *
+ * params == NULL: rt_temporal_default_params' values (max_history 64, sigma_z 0.05, tau_n 0.1,
+ * tau_a 0.05, tau_h 0.5, min_weight 0.25).  d_history ([P] u32) may be NULL.  `prev` is only read.
+ *
+ * Launch: asynchronous on `stream`, one kernel, a plain one-stream call (a pending deferred reduce pass
+ * runs first).  No workspace, no stats.  rt_context_kernel_times reports it as sample_ms, with reduce_ms
+ * 0.  The context's precision setting has no effect.
+ * RT_ERR_INVALID, each answered before any device is touched: null ctx, cam, cam_prev, cur or prev; a
+ * null accum, m2, counts, depth or hits in either frame; albedo or normal given in one frame and NULL
+ * in the other; feature_samples == 0 in either frame; image sizes that differ, are 0, or have
+ * W*H >= 2^32; reserved != 0 (frames or params); max_history outside 1 .. 2^24; a negative or NaN
+ * tolerance; min_weight outside (0, 1]; nn not positive and finite, or an == 0; cur and prev sharing
+ * any buffer pointer. */
+typedef struct rt_temporal_frame {  /* device pointers of one whole image */
+    void* accum;                    /* [P][3] f64 */
+    void* m2;                       /* [P] f64 */
+    uint32_t* counts;               /* [P] u32 */
+    const void* albedo;             /* [P][3] f64, may be NULL */
+    const void* normal;             /* [P][3] f64, may be NULL */
+    const void* depth;              /* [P] f64 */
+    const uint32_t* hits;           /* [P] u32 */
+    uint32_t feature_samples;       /* samples of the feature pass; > 0 */
+    uint32_t reserved;              /* must be 0 */
+} rt_temporal_frame;                /* 64 bytes */
+typedef struct rt_temporal_params {
+    uint32_t max_history;  /* cap on the pseudo-samples a pixel takes over; 1 .. 2^24 */
+    uint32_t reserved;     /* must be 0 */
+    double sigma_z;        /* relative depth tolerance, >= 0 */
+    double tau_n;          /* max squared distance of the mean normals, >= 0 */
+    double tau_a;          /* max squared distance of the mean albedos, >= 0 */
+    double tau_h;          /* max coverage difference, >= 0 */
+    double min_weight;     /* least sum of valid bilinear weights, in (0, 1] */
+} rt_temporal_params;      /* 48 bytes */
+int rt_temporal_default_params(rt_temporal_params* out);
+int rt_temporal_accumulate(rt_context* ctx,
+                           const rt_camera* cam, const rt_temporal_frame* cur,
+                           const rt_camera* cam_prev, const rt_temporal_frame* prev,
+                           const rt_temporal_params* params, uint32_t* d_history, void* stream);
 /* Runs a pending deferred reduce pass (on the out_stream of the call that deferred it); no-op otherwise. */
 int rt_context_flush(rt_context* ctx);
 /* *pending = 1 if the last deferred call left its output pending (direct mode), else 0. */

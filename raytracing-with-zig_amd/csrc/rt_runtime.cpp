@@ -41,6 +41,7 @@
 #include "rt_device.h"
 #include "rt_kernel.h"
 #include "rt_schedule.hpp"
+#include "rt_temporal.h"
 
 void rt_set_last_error(const std::string& msg);
 
@@ -1551,6 +1552,141 @@ int rt_denoise(rt_context* ctx, uint32_t width, uint32_t height, const void* d_a
     HIP_CHECK(hipEventRecord(ctx->done, s));
     ctx->done_valid = true;
     ctx->last_kernel = "denoise";
+    return RT_OK;
+}
+
+// ---- temporal accumulation (rt.h) -------------------------------------------------
+int rt_temporal_default_params(rt_temporal_params* out) {
+    if (!out) { rt_set_last_error("null params output"); return RT_ERR_INVALID; }
+    out->max_history = 64;
+    out->reserved = 0;
+    out->sigma_z = 0.05;
+    out->tau_n = 0.1;
+    out->tau_a = 0.05;
+    out->tau_h = 0.5;
+    out->min_weight = 0.25;
+    return RT_OK;
+}
+
+// One kernel on `stream`; the previous camera's per-call values are computed here (this file is built
+// without contraction, so they have the bits the definition gives them).
+int rt_temporal_accumulate(rt_context* ctx, const rt_camera* cam, const rt_temporal_frame* cur,
+                           const rt_camera* cam_prev, const rt_temporal_frame* prev, const rt_temporal_params* params,
+                           uint32_t* d_history, void* stream) {
+    // the argument checks that need no context come first, the context last: each answers before
+    // anything touches a device
+    if (!cam) { rt_set_last_error("null camera"); return RT_ERR_INVALID; }
+    if (!cam_prev) { rt_set_last_error("null previous camera"); return RT_ERR_INVALID; }
+    if (!cur) { rt_set_last_error("null current frame"); return RT_ERR_INVALID; }
+    if (!prev) { rt_set_last_error("null previous frame"); return RT_ERR_INVALID; }
+    const std::pair<const char*, const rt_temporal_frame*> frames[] = {{"current", cur}, {"previous", prev}};
+    for (const auto& fr : frames) {
+        const rt_temporal_frame* f = fr.second;
+        const char* missing = !f->accum ? "accumulator" : !f->m2 ? "m2" : !f->counts ? "counts" : !f->depth ? "depth"
+                              : !f->hits ? "hits" : nullptr;
+        if (missing) { rt_set_last_error(std::string("null ") + missing + " in the " + fr.first + " frame"); return RT_ERR_INVALID; }
+        if (f->feature_samples == 0) {
+            rt_set_last_error(std::string("feature_samples must be > 0 in the ") + fr.first + " frame");
+            return RT_ERR_INVALID;
+        }
+        if (f->reserved != 0) { rt_set_last_error(std::string("reserved must be 0 in the ") + fr.first + " frame"); return RT_ERR_INVALID; }
+    }
+    if (!cur->albedo != !prev->albedo) { rt_set_last_error("albedo given in one frame and NULL in the other"); return RT_ERR_INVALID; }
+    if (!cur->normal != !prev->normal) { rt_set_last_error("normal given in one frame and NULL in the other"); return RT_ERR_INVALID; }
+    if (cam->image_width != cam_prev->image_width || cam->image_height != cam_prev->image_height) {
+        rt_set_last_error("the image sizes of the two cameras differ");
+        return RT_ERR_INVALID;
+    }
+    if (cam->image_width == 0 || cam->image_height == 0) { rt_set_last_error("width and height must be > 0"); return RT_ERR_INVALID; }
+    const uint64_t P = (uint64_t)cam->image_width * cam->image_height;
+    if (P >= (1ull << 32)) { rt_set_last_error("width * height must be below 2^32"); return RT_ERR_INVALID; }
+    rt_temporal_params prm;
+    rt_temporal_default_params(&prm);
+    if (params) prm = *params;
+    if (prm.reserved != 0) { rt_set_last_error("reserved must be 0"); return RT_ERR_INVALID; }
+    if (prm.max_history < 1 || prm.max_history > (1u << 24)) { rt_set_last_error("max_history must be in 1 .. 2^24"); return RT_ERR_INVALID; }
+    const std::pair<const char*, double> tols[] = {{"sigma_z", prm.sigma_z}, {"tau_n", prm.tau_n}, {"tau_a", prm.tau_a},
+                                                   {"tau_h", prm.tau_h}};
+    for (const auto& t : tols)
+        if (!(t.second >= 0)) {
+            rt_set_last_error(std::string(t.first) + " must be a number >= 0");
+            return RT_ERR_INVALID;
+        }
+    if (!(prm.min_weight > 0 && prm.min_weight <= 1)) { rt_set_last_error("min_weight must be in (0, 1]"); return RT_ERR_INVALID; }
+    rtk::TemporalArgs ta{};
+    const auto dot3 = [](const double* x, const double* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; };
+    for (int k = 0; k < 3; k++) {
+        ta.pixel0[k] = cam->pixel0[k], ta.du[k] = cam->du[k], ta.dv[k] = cam->dv[k], ta.center[k] = cam->center[k];
+        ta.pc[k] = cam_prev->center[k], ta.pdu[k] = cam_prev->du[k], ta.pdv[k] = cam_prev->dv[k];
+        ta.A[k] = cam_prev->pixel0[k] - cam_prev->center[k];
+    }
+    ta.n[0] = ta.pdu[1] * ta.pdv[2] - ta.pdu[2] * ta.pdv[1];
+    ta.n[1] = ta.pdu[2] * ta.pdv[0] - ta.pdu[0] * ta.pdv[2];
+    ta.n[2] = ta.pdu[0] * ta.pdv[1] - ta.pdu[1] * ta.pdv[0];
+    ta.an = dot3(ta.A, ta.n);
+    const double nn = dot3(ta.n, ta.n);
+    if (!(nn > 0 && nn < HUGE_VAL)) {
+        rt_set_last_error("the previous camera's du x dv is degenerate (nn must be positive and finite)");
+        return RT_ERR_INVALID;
+    }
+    if (ta.an == 0 || ta.an != ta.an) { rt_set_last_error("the previous camera's centre lies in its image plane (an must not be 0)"); return RT_ERR_INVALID; }
+    ta.rnn = 1.0 / nn;
+    const void* cp[] = {cur->accum, cur->m2, cur->counts, cur->albedo, cur->normal, cur->depth, cur->hits};
+    const void* pp[] = {prev->accum, prev->m2, prev->counts, prev->albedo, prev->normal, prev->depth, prev->hits};
+    for (const void* x : cp)
+        for (const void* y : pp)
+            if (x && x == y) { rt_set_last_error("the current and the previous frame share a buffer"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    if (rc) return rc;
+    const rt_temporal_frame* src[2] = {cur, prev};
+    rtk::TemporalFrame* dst[2] = {&ta.cur, &ta.prev};
+    for (int f = 0; f < 2; f++) {
+        dst[f]->accum = (double*)src[f]->accum;
+        dst[f]->m2 = (double*)src[f]->m2;
+        dst[f]->counts = src[f]->counts;
+        dst[f]->albedo = (const double*)src[f]->albedo;
+        dst[f]->normal = (const double*)src[f]->normal;
+        dst[f]->depth = (const double*)src[f]->depth;
+        dst[f]->hits = src[f]->hits;
+        dst[f]->fi = 1.0 / (double)src[f]->feature_samples;
+    }
+    ta.sigma_z = prm.sigma_z, ta.tau_n = prm.tau_n, ta.tau_a = prm.tau_a, ta.tau_h = prm.tau_h;
+    ta.min_weight = prm.min_weight;
+    ta.max_history = prm.max_history;
+    ta.W = cam->image_width;
+    ta.H = cam->image_height;
+    ta.history = d_history;
+    if (ctx->timing) {
+        if (ctx->log_used + 1 > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
+        ctx->call_first = ctx->log_used;
+        ctx->log_used += 1;
+        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
+            hipEvent_t e;
+            HIP_CHECK(make_event(&e, true));
+            ctx->events.push_back(e);
+        }
+        ctx->timed_calls = 1;
+    }
+    // nothing of the context is read, but `launched` / `done` are re-recorded below: a previous call on
+    // another stream is waited for first, so the events still cover it
+    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
+    hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
+    if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
+    HIP_CHECK(rtk_launch_temporal(&ta, s));
+    if (ev) {  // the call is reported as the sample kernel; there is no reduce pass (an empty interval)
+        HIP_CHECK(hipEventRecord(ev[1], s));
+        HIP_CHECK(hipEventRecord(ev[2], s));
+        HIP_CHECK(hipEventRecord(ev[3], s));
+    }
+    HIP_CHECK(hipEventRecord(ctx->launched, s));
+    ctx->launched_valid = true;
+    ctx->launched_stream = s;
+    HIP_CHECK(hipEventRecord(ctx->done, s));
+    ctx->done_valid = true;
+    ctx->last_kernel = "temporal_accumulate";
     return RT_OK;
 }
 

@@ -104,7 +104,37 @@ class RtDenoiseParams(C.Structure):
     ]
 
 
+class RtTemporalFrame(C.Structure):
+    """rt_temporal_frame: the device buffers of one whole image (rt.h rt_temporal_accumulate)."""
+    _fields_ = [
+        ("accum", C.c_void_p),
+        ("m2", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("depth", C.c_void_p),
+        ("hits", C.c_void_p),
+        ("feature_samples", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class RtTemporalParams(C.Structure):
+    """rt_temporal_params: the history cap and the tap tests' tolerances (rt.h rt_temporal_accumulate)."""
+    _fields_ = [
+        ("max_history", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("sigma_z", C.c_double),
+        ("tau_n", C.c_double),
+        ("tau_a", C.c_double),
+        ("tau_h", C.c_double),
+        ("min_weight", C.c_double),
+    ]
+
+
 DENOISE_PARAMS_SIZE = 56
+TEMPORAL_FRAME_SIZE = 64
+TEMPORAL_PARAMS_SIZE = 48
 SPHERE_SIZE = 80
 CAMERA_SIZE = 200
 CAMERA_PARAMS_SIZE = 144

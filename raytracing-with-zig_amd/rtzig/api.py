@@ -455,6 +455,119 @@ def render_denoised(cam, spheres, spp, feature_spp=4, params=None, adaptive=None
         r.close()
 
 
+def temporal_params(**overrides):
+    """rt_temporal_params: the library's defaults (rt_temporal_default_params: max_history 64, sigma_z 0.05,
+    tau_n 0.1, tau_a 0.05, tau_h 0.5, min_weight 0.25) with the given fields replaced."""
+    p = abi.RtTemporalParams()
+    check("rt_temporal_default_params", load().rt_temporal_default_params(C.byref(p)))
+    names = [n for n, _ in abi.RtTemporalParams._fields_]
+    for k, v in overrides.items():
+        if k not in names:
+            raise TypeError(f"temporal_params: no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def render_sequence(cams, spheres, spp, feature_spp=4, temporal=None, denoise=None, seed_step=1, device=0,
+                    output="linear", precision="f64"):
+    """A generator over the frames of a camera path through a static scene, on one GPU.  Frame f renders
+    cams[f] with seed = cams[f].seed + f * seed_step (mod 2^64) — a sample's stream is keyed by (seed,
+    pixel, sample), so frames that shared a seed would repeat their random numbers and the history would
+    add no information — as a gather pass of `spp` samples and a feature pass of `feature_spp`; then
+    rt_temporal_accumulate merges the previous frame's merged buffers into it (temporal: temporal_params(),
+    None for the defaults, False to render every frame on its own), and rt_denoise (denoise:
+    denoise_params(), None for the defaults) filters the result.  Two buffer sets take turns.  Yields one
+    dict of numpy arrays per frame:
+        image    (H, W, 3)  the denoised image, linear f64 or rgb8 u8
+        noisy    (H, W, 3)  the merged sums resolved (rt_accum_resolve_counts), same format
+        variance (H, W) f64 the filtered variance of the mean luminance
+        counts   (H, W) u32 samples plus pseudo-samples of each pixel
+        history  (H, W) u32 the pseudo-samples the pixel took over from the previous frame (0 in frame 0)
+    The arguments are checked at the call, before any device work.  samples_per_pixel of the cameras is
+    not used."""
+    if output not in ("linear", "rgb8"):
+        raise ValueError(output)
+    if precision not in _PRECISION:
+        raise ValueError(precision)
+    spp, feature_spp, seed_step = int(spp), int(feature_spp), int(seed_step)
+    if spp < 2 or spp >= 2 ** 32:
+        raise ValueError("spp must be in [2, 2^32) (the variance estimate needs two samples)")
+    if feature_spp < 1 or feature_spp >= 2 ** 32:
+        raise ValueError("feature_spp must be in [1, 2^32)")
+    cams = list(cams)
+    if not cams:
+        raise ValueError("cams: at least one camera")
+    if any(not isinstance(c, RtCamera) for c in cams):
+        raise ValueError("cams: a list of RtCamera")
+    if any((c.image_width, c.image_height) != (cams[0].image_width, cams[0].image_height) for c in cams):
+        raise ValueError("cams: every camera must have the same image size")
+    if cams[0].image_width == 0 or cams[0].image_height == 0:
+        raise ValueError("cams: an empty image")
+    if temporal is True:
+        temporal = None
+    if temporal is not None and temporal is not False and not isinstance(temporal, abi.RtTemporalParams):
+        raise ValueError("temporal: temporal_params(), None or False")
+    if denoise is not None and not isinstance(denoise, abi.RtDenoiseParams):
+        raise ValueError("denoise: denoise_params() or None")
+    return _sequence(cams, spheres, spp, feature_spp, temporal, denoise, seed_step, device, output, precision)
+
+
+def _sequence(cams, spheres, spp, feature_spp, temporal, denoise, seed_step, device, output, precision):
+    import torch
+
+    W, H = cams[0].image_width, cams[0].image_height
+    P = W * H
+    n = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * n)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        r.set_precision(precision)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            sets = []
+            for _ in range(1 if temporal is False else 2):
+                sets.append(dict(accum=torch.empty((P, 3), dtype=torch.float64, device=dev),
+                                 m2=torch.empty(P, dtype=torch.float64, device=dev),
+                                 counts=torch.zeros(P, dtype=torch.int32, device=dev),  # u32 on the device
+                                 albedo=torch.empty((P, 3), dtype=torch.float64, device=dev),
+                                 normal=torch.empty((P, 3), dtype=torch.float64, device=dev),
+                                 depth=torch.empty(P, dtype=torch.float64, device=dev),
+                                 hits=torch.empty(P, dtype=torch.int32, device=dev)))  # u32 on the device
+            ptrs = [dict({k: v.data_ptr() for k, v in s.items()}, feature_samples=feature_spp) for s in sets]
+            odt = torch.float64 if output == "linear" else torch.uint8
+            out = torch.empty((2, H, W, 3), dtype=odt, device=dev)  # denoised, noisy
+            var = torch.empty((H, W), dtype=torch.float64, device=dev)
+            hist = torch.zeros((H, W), dtype=torch.int32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            prev_cam = None
+            for f, cam0 in enumerate(cams):
+                cam = RtCamera.from_buffer_copy(cam0)
+                cam.seed = (cam0.seed + f * seed_step) % 2 ** 64
+                k = f % len(sets)
+                t, d = sets[k], ptrs[k]
+                t["counts"].zero_()  # a new image: the gather pass starts every pixel from 0
+                r.accumulate_pixels(cam, None, spp, d["accum"], d["m2"], d["counts"], stream_ptr=stream)
+                r.features(cam, 0, feature_spp, d["albedo"], d["normal"], d["depth"], d["hits"], stream_ptr=stream)
+                if temporal is not False and f > 0:
+                    r.temporal_accumulate(cam, d, prev_cam, ptrs[1 - k], params=temporal,
+                                          d_history_ptr=hist.data_ptr(), stream_ptr=stream)
+                r.denoise(W, H, d["accum"], d["m2"], d["counts"], out[0].data_ptr(), d_albedo_ptr=d["albedo"],
+                          d_normal_ptr=d["normal"], d_depth_ptr=d["depth"], d_hits_ptr=d["hits"],
+                          feature_samples=feature_spp, params=denoise, output=output, d_var_out_ptr=var.data_ptr(),
+                          stream_ptr=stream)
+                r.resolve_counts(d["accum"], d["counts"], P, out[1].data_ptr(), output=output, stream_ptr=stream)
+                res = out.cpu().numpy()  # waits for the stream
+                frame = {"image": res[0], "noisy": res[1], "variance": var.cpu().numpy(),
+                         "counts": t["counts"].cpu().numpy().view(np.uint32).reshape(H, W),
+                         "history": hist.cpu().numpy().view(np.uint32).reshape(H, W)}
+                r.sync()  # reports a failure the kernel recorded
+                prev_cam = cam
+                yield frame
+    finally:
+        r.close()
+
+
 class DeviceRenderer:
     """Device-resident renderer for one GPU (rt_context): scene uploaded once, rows rendered into
     device memory (e.g. a torch tensor's data_ptr) on a caller-provided HIP stream."""
@@ -624,6 +737,26 @@ class DeviceRenderer:
                                   C.c_void_p(d_hits_ptr or 0), feature_samples,
                                   C.byref(params) if params is not None else None, fmt, C.c_void_p(d_out_ptr or 0),
                                   C.c_void_p(d_var_out_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def temporal_accumulate(self, cam, cur, cam_prev, prev, params=None, d_history_ptr=None, stream_ptr=None):
+        """rt_temporal_accumulate: the previous frame's sums, reprojected through the two cameras and
+        tested against the current frame's guides, merged into the current frame's sums as pseudo-samples.
+        cur and prev: dicts of device pointers — accum, m2, counts (accumulate_pixels' buffers over every
+        pixel), depth, hits and optionally albedo, normal (features()' buffers over all rows) — plus
+        feature_samples.  cur is read and written, prev only read.  params: temporal_params(), None for the
+        defaults.  d_history (W*H u32, optional) receives the pseudo-samples each pixel took over.
+        Asynchronous."""
+        frames = []
+        for d in (cur, prev):
+            extra = set(d) - {"accum", "m2", "counts", "albedo", "normal", "depth", "hits", "feature_samples"}
+            if extra:
+                raise TypeError(f"temporal_accumulate: no frame field {sorted(extra)[0]!r}")
+            frames.append(abi.RtTemporalFrame(**{k: (int(v or 0) if k == "feature_samples" else (v or None))
+                                                 for k, v in d.items()}))
+        check("rt_temporal_accumulate",
+              self.lib.rt_temporal_accumulate(self.ctx, C.byref(cam), C.byref(frames[0]), C.byref(cam_prev),
+                                              C.byref(frames[1]), C.byref(params) if params is not None else None,
+                                              C.c_void_p(d_history_ptr or 0), C.c_void_p(stream_ptr or 0)))
 
     def flush(self):
         """Runs a pending deferred reduce pass (rt_context_flush)."""

@@ -6,7 +6,8 @@ render call goes through the HIP kernel on a gfx950 device (rt_render / rt_rende
 import ctypes as C
 import os
 
-from .abi import RtCamera, RtCameraParams, RtDenoiseParams, RtOptions, RtSphere
+from .abi import (RtCamera, RtCameraParams, RtDenoiseParams, RtOptions, RtSphere, RtTemporalFrame,
+                  RtTemporalParams)
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "librtzig.so")
@@ -28,6 +29,8 @@ EXPORTED = [
     "rt_render_rows_features",
     "rt_denoise_default_params",
     "rt_denoise",
+    "rt_temporal_default_params",
+    "rt_temporal_accumulate",
     "rt_context_flush",
     "rt_context_fold_pending",
     "rt_kernel_name",
@@ -91,6 +94,9 @@ def _declare(lib):
         "rt_denoise_default_params": (C.c_int, [P(RtDenoiseParams)]),
         "rt_denoise": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32,
                                  P(RtDenoiseParams), C.c_uint32, vp, vp, vp]),
+        "rt_temporal_default_params": (C.c_int, [P(RtTemporalParams)]),
+        "rt_temporal_accumulate": (C.c_int, [vp, P(RtCamera), P(RtTemporalFrame), P(RtCamera), P(RtTemporalFrame),
+                                             P(RtTemporalParams), vp, vp]),
         "rt_context_flush": (C.c_int, [vp]),
         "rt_context_fold_pending": (C.c_int, [vp, P(C.c_int)]),
         "rt_kernel_name": (C.c_char_p, [vp]),

@@ -36,6 +36,11 @@
 #              (tools/denoise_cost.py; the "cost" and "quality" objects of its JSON on stdout are kept
 #              as profiles/denoise/cost.json and quality.json).  Its GPU
 #              tests (tests/test_gpu_denoise.py) run with the `tests` step
+#   temporal  what rt_temporal_accumulate costs against rt_denoise at its default levels on config 4's
+#              image, and the RMSE per frame of a 12-frame camera path with the temporal pass off and on
+#              (tools/temporal_cost.py; the "cost" and "quality" objects of its JSON on stdout are kept
+#              as profiles/temporal/cost.json and quality.json).  Its GPU tests
+#              (tests/test_gpu_temporal.py) run with the `tests` step
 #   peak      event-timed VALU peak and issue-cost table (tools/bin/peak_rates, built beforehand)
 #   diag       bounds-checked builds through tools/diag_modes.py (ab/bounds*.so)
 #   uselib     copy $LIB (an ab/*.so build) over the in-tree librtzig.so for the steps after it (on the
@@ -73,6 +78,7 @@ for step in "$@"; do
     adaptive) run adaptive 300 python3 -u tools/adaptive_cost.py ;;
     features) run features 200 python3 -u tools/feature_cost.py ;;
     denoise) run denoise 300 python3 -u tools/denoise_cost.py ;;
+    temporal) run temporal 300 python3 -u tools/temporal_cost.py ;;
     peak)    run peak 300 ./tools/bin/peak_rates ${PEAK_MS:-60} ${PEAK_MODE:-2} ;;
     diag)    run diag 300 python3 -u tools/diag_modes.py raytracing-with-zig_amd/librtzig.so ab/bounds.so --oracle-row ;;
     uselib)  cp "$LIB" raytracing-with-zig_amd/librtzig.so || exit 2; echo "== using $LIB" ;;
