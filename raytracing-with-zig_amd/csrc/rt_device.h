@@ -26,6 +26,24 @@
 
 namespace rtk {
 
+// A valid value nobody chose: for per-lane state that is read only by the lanes that wrote it
+// since.  Unlike an uninitialised variable it is safe to copy and merge (to the compiler it is the
+// result of an instruction), and unlike a default it costs no instruction to set up: the value is
+// whatever the register held.  (__builtin_nondeterministic_value is folded to 0 and materialised.)
+// The asm is volatile so that it stays where it is written and is not hoisted out of a loop.
+template <class T>
+__device__ __forceinline__ T unspecified() {
+    T v;
+    asm volatile("" : "=v"(v));
+    return v;
+}
+// ... where kLean, else the default `d` (the instrumented kernels, rt_kernel.hip path_loop)
+template <bool kLean, class T>
+__device__ __forceinline__ T start_value(T d) {
+    if constexpr (kLean) return unspecified<T>();
+    else return d;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Vec3 (vec.zig:5-136)
 // ------------------------------------------------------------------------------------------------
@@ -213,7 +231,11 @@ __host__ __device__ __forceinline__ uint64_t sm_mix_hd(uint64_t x) {
     return z ^ (z >> 31);
 }
 
-struct Rng {
+// kLean: the forms that leave no register copy behind a draw (next()'s update order, uniform()'s rare
+// test).  The instrumented kernels (kProf) keep the former forms, RngT<false>: the same values, the
+// instructions they had before (rt_kernel.hip path_loop "kLean").
+template <bool kLean>
+struct RngT {
     uint64_t s0, s1, s2, s3;
 
     // DefaultPrng.init(key): Xoshiro256.seed via SplitMix64 (zig std/Random/Xoshiro256.zig)
@@ -237,14 +259,27 @@ struct Rng {
 #else
         const uint64_t t = s1 << 17;
 #endif
-        const uint64_t n1 = xor3_64(s1, s2, s0);
-        const uint64_t n0 = xor3_64(s0, s3, s1);
-        const uint64_t n2 = xor3_64(s2, s0, t);
-        const uint64_t n3 = s3 ^ s1;
-        s0 = n0;
-        s1 = n1;
-        s2 = n2;
-        s3 = rotl64c<45>(n3);
+        if constexpr (kLean) {
+            // In this order s1, s2 and s3 have no reader left when their new value is formed, so a
+            // draw made by some lanes only (the trip loop's third) updates them in place and copies
+            // only s0.  (With every new word formed before any is assigned, two words were copied per
+            // such draw; s0 ^= n3 needs no temporary at all but raised the shipped kernel's SGPR spills.)
+            const uint64_t n0 = xor3_64(s0, s3, s1);
+            const uint64_t n3 = s3 ^ s1;
+            s1 = xor3_64(s1, s2, s0);
+            s2 = xor3_64(s2, s0, t);
+            s0 = n0;
+            s3 = rotl64c<45>(n3);
+        } else {
+            const uint64_t n1 = xor3_64(s1, s2, s0);
+            const uint64_t n0 = xor3_64(s0, s3, s1);
+            const uint64_t n2 = xor3_64(s2, s0, t);
+            const uint64_t n3 = s3 ^ s1;
+            s0 = n0;
+            s1 = n1;
+            s2 = n2;
+            s3 = rotl64c<45>(n3);
+        }
         return r;
     }
     // Random.float(f64) (zig std/Random.zig): mantissa = low 52 bits, exponent from leading zeros;
@@ -257,6 +292,11 @@ struct Rng {
         // ohi = (hi & 0xfffff) | (1022 - lz) << 20: the exponent field e = 1022*2^20 - lz*2^20 by one
         // v_mad_i32_i24 (lz <= 11; -2^20 is a valid signed 24-bit factor), then one v_bfi_b32
         // (VOP3 takes no literals and one SGPR: the 1022 << 20 addend lives in a VGPR)
+        // The rare test (>= 12 leading zeros, p = 2^-12 per draw) is taken here, before the bit
+        // select, so that the select is the last reader of `hi` and the result is formed in the word's
+        // own register pair (tested afterwards, every draw copied the word's low half to a new pair).
+        bool rare = false;
+        if constexpr (kLean) rare = hi < (1u << 20);
         uint32_t e, ohi;
         asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(e) : "v"((uint32_t)__builtin_clz(hi)), "s"(-(1 << 20)), "v"(1022u << 20));
 #if RTZIG_RNG_FORM >= 2
@@ -267,10 +307,15 @@ struct Rng {
         asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(ohi) : "s"(0xfffffu), "v"(hi), "v"(e));
 #endif
         double res = __builtin_bit_cast(double, u32x2{(uint32_t)rnd, ohi});
-        // >= 12 leading zeros (p = 2^-12 per draw): the fast result is computed for every lane and
-        // the rare lanes are redone, behind a wave-uniform test so the common case has no
-        // exec-mask branch
-        if (__builtin_expect(__ballot(hi < (1u << 20)) != 0, 0)) {
+        // the fast result is computed for every lane and the rare lanes are redone, behind a
+        // wave-uniform test so the common case has no exec-mask branch.  A rare lane's word is its
+        // result's low 52 bits (its hi has no bit above bit 19), so the word itself is not kept.
+        if constexpr (kLean) {
+            if (__builtin_expect(__ballot(rare) != 0, 0)) {
+                RTK_MARK("rare");
+                if (rare) res = uniform_slow(__builtin_bit_cast(uint64_t, res) & ((1ULL << 52) - 1));
+            }
+        } else if (__builtin_expect(__ballot(hi < (1u << 20)) != 0, 0)) {
             RTK_MARK("rare");
             if (hi < (1u << 20)) res = uniform_slow(rnd);
         }
@@ -297,6 +342,7 @@ struct Rng {
     // the same bits with one f64 op instead of two (u may be subnormal: 2u is still exact).
     __device__ __forceinline__ double range_pm1() { return __builtin_fma(2.0, uniform(), -1.0); }
 };
+using Rng = RngT<true>;
 
 // key(seed, pixel, sample) = mix(mix(seed) ^ (pixel << 32 | sample)); seed_mix = mix(seed) is
 // hoisted to the host.  For a fixed seed the map (pixel, sample) -> key is a bijection.

@@ -88,7 +88,8 @@ __device__ __forceinline__ double dw2d(uint32_t lo, uint32_t hi) {
 // camera_finish adds the disk sample (defocusDiskSample, :212-215) drawn by path_loop's trip loop.
 // Camera constants are read from the kernarg segment by scalar loads at each use (KernelParams
 // must be the kernel's first argument).
-__device__ __forceinline__ bool camera_start(uint32_t i, uint32_t j, Rng& g, Ray& r) {
+template <class RngX>
+__device__ __forceinline__ bool camera_start(uint32_t i, uint32_t j, RngX& g, Ray& r) {
     u32x16 A;  // dwords 6..21 of KernelParams: center, pixel0, du.x, du.y
     u32x8 B;   // dwords 22..29: du.z, dv
     u32x2 C;   // dwords 42..43: defocus_angle
@@ -118,7 +119,8 @@ __device__ __forceinline__ bool camera_start(uint32_t i, uint32_t j, Rng& g, Ray
 }
 // The seed window's half of camera_start: sampleSquare's draws and the pixel sample point
 // (camera.zig:190-193, 203-209), the same operations as above.
-__device__ __forceinline__ v3 pixel_sample_point(uint32_t i, uint32_t j, Rng& g) {
+template <class RngX>
+__device__ __forceinline__ v3 pixel_sample_point(uint32_t i, uint32_t j, RngX& g) {
     u32x16 A;  // dwords 12..27 of KernelParams: pixel0, du, dv.x, dv.y
     u32x2 B;   // dwords 28..29: dv.z
     const uint64_t kp = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
@@ -211,8 +213,10 @@ __device__ __forceinline__ bool near_zero(f3 v) { return v.x < 1e-8f && v.y < 1e
 __device__ __forceinline__ v3 to64(f3 a) { return v3{a.x, a.y, a.z}; }
 // U[0, 1) from the top 24 bits of one Xoshiro256++ word (exact in f32); uniform2 takes two from one
 // word (the top 24 bits of each 32-bit half), halving the generator work of paired draws
-__device__ __forceinline__ float uniform(Rng& g) { return (float)(uint32_t)(g.next() >> 40) * 0x1p-24f; }
-__device__ __forceinline__ void uniform2(Rng& g, float& a, float& b) {
+template <class RngX>
+__device__ __forceinline__ float uniform(RngX& g) { return (float)(uint32_t)(g.next() >> 40) * 0x1p-24f; }
+template <class RngX>
+__device__ __forceinline__ void uniform2(RngX& g, float& a, float& b) {
     const uint64_t w = g.next();
     a = (float)(uint32_t)(w >> 40) * 0x1p-24f;
     b = (float)((uint32_t)w >> 8) * 0x1p-24f;
@@ -229,7 +233,8 @@ constexpr int kFcam = (int)offsetof(KernelParams, fcam);
 static_assert(kFcam % 4 == 0, "fcam kernarg offset");
 __device__ __forceinline__ float fw(uint32_t w) { return __builtin_bit_cast(float, w); }
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bool camera_start(uint32_t i, uint32_t j, Rng& g, fm::Ray& r) {
+template <class RngX>
+__device__ __forceinline__ bool camera_start(uint32_t i, uint32_t j, RngX& g, fm::Ray& r) {
 #pragma clang fp contract(fast)
     u32x16 A;  // fcam[0..15]
     u32x4 B;   // fcam[16..19]
@@ -756,6 +761,12 @@ struct BvhWalker {
     }
 
     static constexpr bool kCanSuspend = true;
+    // the word of the suspended-walk state itself, or a working copy of it (run_f64)
+    template <bool kInPlace, class T>
+    __device__ __forceinline__ static T& lean_ref(T& in_state, T& work) {
+        if constexpr (kInPlace) return in_state;
+        else return work;
+    }
     struct State {  // a suspended walk (dynamic fetch)
         int32_t cur;
         StackT* top;
@@ -1020,19 +1031,41 @@ struct BvhWalker {
     __device__ __forceinline__ int run_f64(const Ray& r, double t_min, double t_max, double* t_hit, PR& pr, State& st,
                                            const bool resume, const bool refetch) const {
         const double a = len_sq(r.dir);
-        double closest = t_max;
-        uint32_t best = 0;
+        // kLean (the uninstrumented kernels): closest, best, cur and top live in `st` itself: a
+        // resumed lane continues on the values it left there, a starting lane sets them below, and a
+        // lane that suspends has none of them to save.  (Working copies cost a copy per word for the
+        // resumed lanes at entry and a select per word for the suspended ones at exit; `st` is read
+        // again only by a lane that suspended.)  `found` stays a working copy: a lane mask during
+        // the walk, a 0 / 1 word in `st` (kept in `st` as well, the shipped kernel's SGPR spills rose
+        // from 15 to 25).  The instrumented kernels keep working copies of all five (path_loop "kLean").
+        constexpr bool kLean = std::is_same_v<PR, Prof<0>>;
+        double closest_w;
+        uint32_t best_w;
+        double& closest = lean_ref<kLean>(st.closest, closest_w);
+        uint32_t& best = lean_ref<kLean>(st.best, best_w);
         bool found = false;
-        if constexpr (kSusp) {
-            if (resume) {
-                closest = st.closest;
-                best = st.best;
-                found = st.found;
+        if constexpr (!kLean) {
+            closest = t_max;
+            best = 0;
+            if constexpr (kSusp) {
+                if (resume) {
+                    closest = st.closest;
+                    best = st.best;
+                    found = st.found;
+                }
             }
+        } else if constexpr (kSusp) {
+            if (resume) found = st.found;
         }
         const LeafFilter lfilt = LeafFilter::make(a, t_min);
         const RayDiv ad(a);
         RTK_MARK("always");
+        if constexpr (kLean) {
+            if (!(kSusp && resume)) {
+                closest = t_max;
+                best = unspecified<uint32_t>();  // read only once `found`
+            }
+        }
         if (kSusp && resume) {
             // the always-list and the far-origin check ran when this walk started
         } else if (n_always <= 4) {
@@ -1102,12 +1135,23 @@ struct BvhWalker {
 
         // stack: entry 0 holds kEnd (written once per lane at kernel start), entries 1..sp the
         // pushed far children; a pop reads entry sp, so popping the empty stack yields kEnd
-        StackT* top = stack;  // this lane's stack entry sp (entry i at stack[i * kStride])
-        int32_t cur = far ? kEnd : 0;  // root
-        if constexpr (kSusp) {
-            if (resume) {
-                top = st.top;
-                cur = st.cur;
+        StackT* top_w;
+        int32_t cur_w;
+        StackT*& top = lean_ref<kLean>(st.top, top_w);  // this lane's stack entry sp (entry i at stack[i * kStride])
+        int32_t& cur = lean_ref<kLean>(st.cur, cur_w);
+        if constexpr (kLean) {
+            if (!(kSusp && resume)) {
+                top = stack;
+                cur = far ? kEnd : 0;  // root
+            }
+        } else {
+            top = stack;
+            cur = far ? kEnd : 0;  // root
+            if constexpr (kSusp) {
+                if (resume) {
+                    top = st.top;
+                    cur = st.cur;
+                }
             }
         }
         // while-while (Aila & Laine 2009): every lane advances through internal nodes until it
@@ -1199,10 +1243,12 @@ struct BvhWalker {
         }
         if constexpr (kSusp) {
             if (cur != kEnd) {
-                st.cur = cur;
-                st.top = top;
-                st.closest = closest;
-                st.best = best;
+                if constexpr (!kLean) {
+                    st.cur = cur;
+                    st.top = top;
+                    st.closest = closest;
+                    st.best = best;
+                }
                 st.found = found;
                 return kSuspended;
             }
@@ -1222,7 +1268,8 @@ struct WalkerPrecision<W, std::void_t<decltype(W::kFast)>> {
     static constexpr bool kF32 = W::kFast;
 };
 // one trip of the shared rejection loop: randomUnitVec (3 draws) or randomInUnitDisk (2 draws)
-__device__ __forceinline__ void trip_f32(Rng& g, bool wr, float& ux, float& uy, float& uz, float& uls, bool& got,
+template <class RngX>
+__device__ __forceinline__ void trip_f32(RngX& g, bool wr, float& ux, float& uy, float& uz, float& uls, bool& got,
                                          bool& dgot) {
 #pragma clang fp contract(fast)
     fm::uniform2(g, ux, uy);
@@ -1263,8 +1310,9 @@ __device__ __forceinline__ void scatter_f32(float ux, float uy, float uz, float 
     }
 }
 // rayColor's loop body after the walk (camera.zig:157-177) in f32
+template <class RngX>
 __device__ __forceinline__ void shade_f32(int k, float t, const GeoRec* __restrict__ geo_orig,
-                                          const MatRec* __restrict__ mat_g, Rng& g, fm::Ray& r, fm::f3& att, fm::f3& col,
+                                          const MatRec* __restrict__ mat_g, RngX& g, fm::Ray& r, fm::f3& att, fm::f3& col,
                                           bool& done, bool& pending, bool& sc_metal, float& sc_fuzz, fm::f3& sc_nrm,
                                           fm::f3& sc_refl, uint32_t& bounce) {
 #pragma clang fp contract(fast)
@@ -1377,9 +1425,16 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
     using V = std::conditional_t<kF32, fm::f3, v3>;
 
     // per-lane path state
+    // kLean: the forms without merge copies: values read only by the lanes that wrote
+    // them start unspecified, the generator and the walk update their state in place.  The
+    // instrumented kernels keep the former forms and compile to the instructions they had before:
+    // with the lean forms the instrumented ring-mode kernel faulted on the MI355X in a 500-spp
+    // config-4 frame (an illegal memory access; the 100-spp instrumented frame and the suite's
+    // instrumented launches ran), and the cause was not found.
+    constexpr bool kLean = !kProf;
     bool active = false;
     uint32_t myslot = 0, mi = 0;  // the unit slot and item of the lane's path (its ring position)
-    Rng g;
+    RngT<kLean> g;
     RayT r;
     V att = V{1, 1, 1};
     uint32_t bounce = 0;
@@ -1448,7 +1503,8 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
         // ---- hand new items to lanes without a path (wave-uniform control flow) ----------------
         RTK_MARK("handout");
         bool fresh = false;
-        uint32_t fq = 0, fs = 0;  // pixel (launch-local) and sample of a freshly handed item
+        // pixel (launch-local) and sample of a freshly handed item: read by the fresh lanes only
+        uint32_t fq = start_value<kLean, uint32_t>(0), fs = start_value<kLean, uint32_t>(0);
         const bool was_drained = us.drained;
         // RTZIG_REFILL_MIN (A/B knob, default 0): hand out items only once at least that many lanes
         // are free (or the wave has no path left), so seeding / getRay run with fuller waves
@@ -1495,6 +1551,7 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
                         wkey[0] = kt;
                         wkey[1] = ks;
                     }
+                    if constexpr (kLean) __builtin_amdgcn_wave_barrier();  // the key store stays ahead of the next pass's key read
                     uint32_t q = kt * 64 + lane;  // past the launch's last pixel: computed, never read
                     uint32_t ksl = ks;            // the sample this lane's entry is keyed with
                     if constexpr (kGather) {
@@ -1507,7 +1564,7 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
                     const uint32_t row_local = fastdiv(q, p.div_width);
                     const uint32_t i = q - row_local * W;
                     const uint32_t j = kGather ? row_local : p.row0 + row_local * p.row_step;
-                    Rng gw;
+                    RngT<kLean> gw;
                     gw.seed(sample_key(p.seed_mix, (uint64_t)j * W + i, ksl));
                     uint64_t w[7];
                     if constexpr (kF32) {  // fast mode: camera_start's f32 ray direction (2 planes unused)
@@ -1535,6 +1592,11 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
                         wp[(2 * k) * 64 + lane] = (uint32_t)w[k];
                         wp[(2 * k + 1) * 64 + lane] = (uint32_t)(w[k] >> 32);
                     }
+                    // The window is handed from lane to lane through LDS within one wave: in-order LDS
+                    // makes it safe in hardware, and these barriers (no instruction) keep the compiler
+                    // from moving another lane's reads above the fill's stores, or a later fill's
+                    // stores above a take's reads.
+                    if constexpr (kLean) __builtin_amdgcn_wave_barrier();
                     RTK_MARK("seed");
                 }
                 if constexpr (kLanes) ++n_take;
@@ -1563,6 +1625,7 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
                     att = V{1, 1, 1};
                     bounce = 0;
                 }
+                if constexpr (kLean) __builtin_amdgcn_wave_barrier();  // the take's reads stay ahead of the next fill
                 todo &= ~__ballot(mine);
             }
         } else if (fresh) {
@@ -1608,7 +1671,11 @@ __device__ __forceinline__ void path_loop(const KernelParams& p, const Walker& w
         // so the bits do not change.
         bool done = false;
         V col = V{0, 0, 0};
-        Real ux = 0, uy = 0, uz = 0, uls = 1;
+        // The candidate is read only under got / dgot, by the lanes whose accepted trip wrote it: it
+        // starts as an unspecified (but valid) value, so no default is materialised for the lanes
+        // that do not draw, in any of the unrolled trips.
+        Real ux = start_value<kLean, Real>(0), uy = start_value<kLean, Real>(0), uz = start_value<kLean, Real>(0),
+             uls = start_value<kLean, Real>(1);
         bool got = false, dgot = false;
         // One trip for the lanes still drawing; leaves the loop when no lane of the wave is.  (A macro:
         // written as a lambda or a function taking the flags by reference, got / dgot went to
