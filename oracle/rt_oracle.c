@@ -476,6 +476,39 @@ EXPORT int oracle_render_b(const rt_camera* cam, const rt_sphere* spheres, size_
     return 0;
 }
 
+/* Mode B's sample loop over samples [sample_begin, sample_begin + sample_count) of the same rows,
+ * added in sample order onto the unscaled sums already in sums_inout ([n_rows*W][3]); nothing is
+ * scaled.  The absolute sample number sample_begin + s is formed in u64 and handed to the key
+ * as u64, so no 32-bit addition can wrap on the way (the key itself uses its low 32 bits: the ABI
+ * stops at sample 2^32 - 2).  cam->samples_per_pixel and pixel_samples_scale are not used. */
+EXPORT int oracle_accumulate_b(const rt_camera* cam, const rt_sphere* spheres, size_t n, uint32_t row0,
+                               uint32_t row_step, uint32_t n_rows, uint64_t sample_begin,
+                               uint64_t sample_count, double* sums_inout, uint64_t* rays_out,
+                               int n_threads) {
+    osphere* sp = load_spheres(spheres, n);
+    const uint32_t W = cam->image_width;
+    uint64_t rays = 0;
+#pragma omp parallel for schedule(dynamic, 1) reduction(+ : rays) num_threads(n_threads > 0 ? n_threads : 1)
+    for (uint32_t k = 0; k < n_rows; k++) {
+        const uint32_t j = row0 + k * row_step;
+        for (uint32_t i = 0; i < W; i++) {
+            const uint64_t pixel = (uint64_t)j * W + i;
+            double* o = sums_inout + 3 * ((size_t)k * W + i);
+            v3 sum = V(o[0], o[1], o[2]);
+            for (uint64_t s = 0; s < sample_count; s++) {
+                xoshiro g;
+                xoshiro_seed(&g, oracle_sample_key(cam->seed, pixel, sample_begin + s));
+                const ray_t r = get_ray(cam, i, j, &g);
+                sum = add(sum, ray_color(sp, n, r, cam, &g, &rays));
+            }
+            o[0] = sum.x; o[1] = sum.y; o[2] = sum.z;
+        }
+    }
+    free(sp);
+    if (rays_out) *rays_out = rays;
+    return 0;
+}
+
 /* ------------------------------------------------------------------------------------------------
  * Color.toRgb (color.zig:63-80) and PPM.saveBinary (ppm.zig:42-60)
  * ---------------------------------------------------------------------------------------------- */

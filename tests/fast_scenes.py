@@ -89,6 +89,13 @@ def large():
             .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(2).setBounceMax(3).build())
 
 
+def with_camera(cam, **fields):
+    """The camera with some rt_camera fields replaced (t_max, seed): the world stays as generated."""
+    for k, v in fields.items():
+        setattr(cam.cam, k, v)
+    return cam
+
+
 # name -> camera factory: every scene the GPU tests hold to the rule; the CPU test checks the input
 # condition share_F32(1e-3) <= INPUT_CAP on each.
 # More than one sample per pixel: a pixel average differs as soon as one of its samples diverges, so
@@ -109,6 +116,11 @@ SCENES = {
     "final_w64_spp3_d2": lambda: final(2, width=64, spp=3),
     "final_w64_spp17_d1": lambda: final(1, width=64, spp=17),
     "chapter13_w64_spp17": lambda: chapter13(width=64, spp=17),
+    # a finite interval: the f32 cast of t_max starts `closest`; about half the hits of the final scene
+    # lie beyond t = 1.2, and chapter 13's ground and far spheres beyond 1.1
+    "final_d2_tmax1.2": lambda: with_camera(final(2), t_max=1.2),
+    "chapter13_tmax1.1": lambda: with_camera(chapter13(), t_max=1.1),
+    "final_d2_seed63": lambda: with_camera(final(2), seed=1 << 63),  # a seed above 32 bits
 }
 
 

@@ -27,6 +27,8 @@ class Oracle:
         L.oracle_render_a.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, P(C.c_uint64), dp, P(C.c_uint64)]
         L.oracle_render_b.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, C.c_uint32, C.c_uint32,
                                       C.c_uint32, dp, P(C.c_uint64), C.c_int]
+        L.oracle_accumulate_b.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, C.c_uint32, C.c_uint32,
+                                          C.c_uint32, C.c_uint64, C.c_uint64, dp, P(C.c_uint64), C.c_int]
         L.oracle_render_f.argtypes = [P(RtCamera), P(RtSphere), C.c_size_t, C.c_int, C.c_uint32, C.c_uint32,
                                       C.c_uint32, dp, P(C.c_uint64), C.c_int]
         L.oracle_f_last_draws.restype = C.c_uint64
@@ -86,6 +88,22 @@ class Oracle:
         rays = C.c_uint64()
         self.L.oracle_render_b(C.byref(cam), spheres, len(spheres), row0, row_step, n_rows,
                                out.ctypes.data_as(dp), C.byref(rays), threads)
+        return out, rays.value
+
+    def accumulate_b(self, cam, spheres, sample_begin, sample_count, sums=None, row0=0, row_step=1,
+                     n_rows=None, threads=1):
+        """Mode B's samples [sample_begin, sample_begin + sample_count) added, in sample order, onto
+        `sums` ((n_rows, W, 3) unscaled f64 sums; None: zeros): (a new array of sums, rays).  `sums` is
+        not modified."""
+        W, H = cam.image_width, cam.image_height
+        if n_rows is None:
+            n_rows = (H - row0 + row_step - 1) // row_step
+        out = np.zeros((n_rows, W, 3)) if sums is None else np.array(sums, np.float64).reshape(n_rows, W, 3)
+        assert out.flags.c_contiguous and out is not sums
+        rays = C.c_uint64()
+        rc = self.L.oracle_accumulate_b(C.byref(cam), spheres, len(spheres), row0, row_step, n_rows,
+                                        sample_begin, sample_count, out.ctypes.data_as(dp), C.byref(rays), threads)
+        assert rc == 0, rc
         return out, rays.value
 
     def render_f(self, cam, spheres, real_bits=64, row0=0, row_step=1, n_rows=None, threads=1, draws=None):

@@ -93,6 +93,17 @@ def test_materials_per_sample(oracle, scene):
     check_scene(oracle, scene, scene)
 
 
+@pytest.mark.parametrize("scene", ["final_d2_tmax1.2", "chapter13_tmax1.1", "final_d2_seed63"])
+def test_finite_interval_max_and_a_64_bit_seed(oracle, scene):
+    """A finite t_max (fast mode starts `closest` from its f32 cast) and a seed with bit 63 set, held to
+    the same rule.  The references show the inputs are not the default ones: the finite interval or
+    the other seed changes more than a tenth of oracle F64's pixels."""
+    check_scene(oracle, scene, scene)
+    base = "chapter13" if scene.startswith("chapter13") else "final_d2"
+    moved = (pair_of(oracle, scene)[1][0] != pair_of(oracle, base)[1][0]).any(axis=-1).mean()
+    assert moved > 0.10, moved
+
+
 @pytest.mark.parametrize("scene", ["ground_99.9", "ground_100.1", "c1_straddle"])
 def test_always_list_split(oracle, scene):
     """always_f32's f32 / f64 split at r^2 < 1e4 and |c|_1 < 1e4: the same scene on a ground of radius

@@ -327,7 +327,7 @@ def synthetic(pattern, n):
     return accum, m2, counts
 
 
-def select_numpy(accum, m2, counts):
+def select_numpy(accum, m2, counts, min_c=MIN_C, max_c=MAX_C, tol=TOL, floor=FLOOR):
     with np.errstate(all="ignore"):
         n = counts.astype(np.float64)
         S = (accum[:, 0] + accum[:, 1]) + accum[:, 2]
@@ -335,9 +335,9 @@ def select_numpy(accum, m2, counts):
         v = m2 - S * mean
         v = np.where(v < 0, 0.0, v)
         sem = np.sqrt((v / (n - 1)) / n)
-        err = sem / np.where(mean > FLOOR, mean, FLOOR)
+        err = sem / np.where(mean > floor, mean, floor)
         err = np.where(counts < 2, 0.0, err)
-        sel = (counts < MIN_C) | ((counts < MAX_C) & ~(err <= TOL))
+        sel = (counts < min_c) | ((counts < max_c) & ~(err <= tol))
     return np.flatnonzero(sel), err
 
 

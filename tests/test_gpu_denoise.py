@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import denoise_ref
+import domain_values
 import rtzig
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +21,7 @@ LEVELS = [0, 1, 3, 6]                                   # at 6 the step of 32 ex
 FORMS = [None, "tile", "direct"]                        # RTZIG_DENOISE_FORM: the default choice and both forced
 ALT = dict(sigma_l=1.5, sigma_n=3.0, sigma_a=0.75, sigma_z=0.4, sigma_h=0.0, epsilon=1e-3)
 FS = 4                                                  # feature samples of the synthetic guides
-PATTERNS = ["smooth", "random", "constant", "counts", "v-negative", "zero-variance", "hits-zero"]
+PATTERNS = ["smooth", "random", "constant", "counts", "v-negative", "zero-variance", "hits-zero", "huge-counts"]
 
 
 def synthetic(pattern, W, H):
@@ -32,7 +33,8 @@ def synthetic(pattern, W, H):
       counts         counts of 0, 1, 2 and uneven larger values
       v-negative     m2 slightly below S * mean: the variance clamps to 0
       zero-variance  dyadic values, m2 == S * mean exactly: v == 0, the luminance weight is 1 / epsilon wide
-      hits-zero      pixels without a hit (z == 0, coverage 0) next to hit pixels"""
+      hits-zero      pixels without a hit (z == 0, coverage 0) next to hit pixels
+      huge-counts    counts of 2^31 and 2^32 - 1 beside 16: the u32 converts to double unsigned"""
     P = W * H
     rng = np.random.default_rng(1000 * W + H + len(pattern))
     j, i = np.divmod(np.arange(P), W)
@@ -58,6 +60,8 @@ def synthetic(pattern, W, H):
         base, noise = rng.integers(0, 9, (P, 3)) / 8.0, 1.0
     elif pattern == "hits-zero":
         hits = np.where((i // 3 + j // 2) % 2 == 0, 0, rng.integers(1, FS + 1, P))
+    elif pattern == "huge-counts":
+        counts = np.array([2 ** 31, 2 ** 32 - 1, 16], np.int64)[(i + 2 * j) % 3] if P > 1 else np.array([2 ** 31])
     c = counts.astype(np.float64)
     accum = base * noise * c[:, None]
     S = (accum[:, 0] + accum[:, 1]) + accum[:, 2]
@@ -77,7 +81,9 @@ class Device:
 
     def __init__(self, W, H, host):
         self.W, self.H, self.host = W, H, host
-        self.t = {k: torch.from_numpy(np.ascontiguousarray(v.astype(np.int32) if k in ("counts", "hits") else v)).to(DEV)
+        # counts and hits are u32 on the device: the low 32 bits, carried in an int32 tensor
+        self.t = {k: torch.from_numpy(np.ascontiguousarray(v.astype(np.uint32).view(np.int32) if k in ("counts", "hits")
+                                                           else v)).to(DEV)
                   for k, v in host.items()}
         self.before = {k: v.clone() for k, v in self.t.items()}
 
@@ -143,6 +149,64 @@ def test_bits_against_numpy(rend, monkeypatch, shape, pattern):
     if pattern == "constant" and W * H > 1:
         c5, _ = d.ref()
         assert np.abs(c5 - [0.4, 0.5, 0.3]).max() < 1e-12  # a constant image stays (to rounding) constant
+
+
+@pytest.mark.parametrize("shape, levels", [((37, 23), 16), ((300, 2), 9), ((2, 100), 9)],
+                         ids=["37x23-levels16", "300x2-levels9", "2x100-levels9"])
+def test_every_level_rt_h_allows_and_long_thin_images(rend, monkeypatch, shape, levels):
+    """levels = 16 (step 32768, the most rt.h allows) and two long thin images at levels = 9: step 256
+    still has taps inside the 300-wide image, and a step's lattice has more than one 32 x 8 tile at
+    steps 1 to 8 of 300 x 2 and at step 8 of 2 x 100, which no image up to 70 x 45 reaches beyond
+    step 4.  Level counts from 0 up to `levels`, all three forms."""
+    W, H = shape
+    for pattern in ("smooth", "huge-counts"):
+        d = Device(W, H, synthetic(pattern, W, H))
+        for lv in sorted({0, 1, 4, 7, levels - 1, levels}):
+            want_c, want_v = d.ref(levels=lv)
+            assert np.isfinite(want_c).all() and np.isfinite(want_v).all()
+            for form in FORMS:
+                if form is None:
+                    monkeypatch.delenv("RTZIG_DENOISE_FORM", raising=False)
+                else:
+                    monkeypatch.setenv("RTZIG_DENOISE_FORM", form)
+                got_c, got_v = d.run(rend, rtzig.denoise_params(levels=lv))
+                assert same_bits(got_c, want_c) and same_bits(got_v, want_v), (pattern, shape, lv, form)
+        assert d.unchanged()
+    if W == 300:  # the large steps do reach pixels: level 9 (step 256) still moves the image
+        assert not same_bits(d.ref(levels=8)[0], d.ref(levels=9)[0])
+
+
+def test_huge_counts_reach_the_prepare_pass_unsigned():
+    """What the huge-counts pattern is for, on the reference: its prepared colours are those of the
+    same means at count 16 to rounding, where a count read as a signed 32-bit number would flip the
+    sign (2^31) or scale by -1 (2^32 - 1)."""
+    W, H = 37, 23
+    h = synthetic("huge-counts", W, H)
+    assert set(np.unique(h["counts"])) == {16, 2 ** 31, 2 ** 32 - 1}
+    c, var = denoise_ref.prepare(W, H, h["accum"], h["m2"], h["counts"])[:2]
+    assert (c > 0.05).all() and (c < 1.0).all() and (var >= 0).all()
+    signed = h["counts"].astype(np.uint32).view(np.int32).astype(np.int64)
+    assert (denoise_ref.prepare(W, H, h["accum"], h["m2"], signed)[0] < 0).any()
+
+
+def test_rgb8_sink_on_the_byte_boundaries(rend, oracle):
+    """The denoiser's RGB8 sink at levels = 0 (the prepared colour, counts of 1) on every input at which
+    Color.toRgb changes its byte, and on zero, negative, huge and subnormal sums.  Finite values only:
+    finite sums are the contract."""
+    vals = domain_values.channel_values(finite_only=True)
+    W, H = len(vals) // 2, 2
+    P = W * H
+    assert P == len(vals) and np.isfinite(vals).all()
+    accum = domain_values.pixels(P, finite_only=True)
+    host = dict(accum=accum, m2=np.zeros(P), counts=np.ones(P, np.int64), albedo=np.zeros((P, 3)),
+                normal=np.zeros((P, 3)), depth=np.zeros(P), hits=np.zeros(P, np.int64))
+    d = Device(W, H, host)
+    p0 = rtzig.denoise_params(levels=0)
+    lin, var = d.run(rend, p0)
+    assert same_bits(lin, accum) and (var == 0).all()  # x * (1.0 / 1.0) is x; one sample has no variance
+    rgb, _ = d.run(rend, p0, output="rgb8", var=False)
+    assert np.array_equal(rgb, oracle.to_rgb8(accum)), np.argwhere(rgb != oracle.to_rgb8(accum))[:8].tolist()
+    assert len(np.unique(rgb)) == 256 and d.unchanged()
 
 
 def test_the_patterns_reach_partial_weights_and_zero_weights():

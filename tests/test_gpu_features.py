@@ -46,6 +46,29 @@ def get_ray(cam, i, j, u):
     return origin, [ps[c] - origin[c] for c in range(3)]
 
 
+def add_sample(oracle, cam, spheres, s, alb, nrm, dep, hits):
+    """Adds sample s of every pixel, in place, to the four sums (albedo (H*W, 3), normal (H*W, 3),
+    depth (H*W), hits (H*W) u32)."""
+    W, H = cam.image_width, cam.image_height
+    for p in range(H * W):
+        j, i = divmod(p, W)
+        u = [float(x) for x in oracle.random_doubles(oracle.sample_key(cam.seed, p, s), MAX_DRAWS)]
+        orig, d = get_ray(cam, i, j, u)
+        k, t = oracle.world_hit(spheres, orig, d, cam.t_min, cam.t_max)
+        if k < 0:
+            continue  # a miss contributes exactly nothing
+        sp = spheres[k]
+        rec = oracle.sphere_hit(sp, orig, d, cam.t_min, cam.t_max)
+        assert rec is not None and rec["t"] == t
+        a = (1.0, 1.0, 1.0) if sp.material == RT_DIELECTRIC else tuple(sp.albedo)
+        depth = t * math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+        for c in range(3):
+            alb[p, c] = alb[p, c] + a[c]
+            nrm[p, c] = nrm[p, c] + rec["normal"][c]
+        dep[p] = dep[p] + depth
+        hits[p] += 1
+
+
 def reference(oracle, cam, spheres, n_samples):
     """Prefix sums: ref[n] = (albedo (H*W, 3), normal (H*W, 3), depth (H*W), hits (H*W) u32) after
     samples [0, n), for n = 0..n_samples."""
@@ -54,23 +77,7 @@ def reference(oracle, cam, spheres, n_samples):
     dep, hits = np.zeros(H * W), np.zeros(H * W, np.uint32)
     ref = [(alb.copy(), nrm.copy(), dep.copy(), hits.copy())]
     for s in range(n_samples):
-        for p in range(H * W):
-            j, i = divmod(p, W)
-            u = [float(x) for x in oracle.random_doubles(oracle.sample_key(cam.seed, p, s), MAX_DRAWS)]
-            orig, d = get_ray(cam, i, j, u)
-            k, t = oracle.world_hit(spheres, orig, d, cam.t_min, cam.t_max)
-            if k < 0:
-                continue  # a miss contributes exactly nothing
-            sp = spheres[k]
-            rec = oracle.sphere_hit(sp, orig, d, cam.t_min, cam.t_max)
-            assert rec is not None and rec["t"] == t
-            a = (1.0, 1.0, 1.0) if sp.material == RT_DIELECTRIC else tuple(sp.albedo)
-            depth = t * math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
-            for c in range(3):
-                alb[p, c] = alb[p, c] + a[c]
-                nrm[p, c] = nrm[p, c] + rec["normal"][c]
-            dep[p] = dep[p] + depth
-            hits[p] += 1
+        add_sample(oracle, cam, spheres, s, alb, nrm, dep, hits)
         ref.append((alb.copy(), nrm.copy(), dep.copy(), hits.copy()))
     return ref
 

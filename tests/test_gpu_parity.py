@@ -519,16 +519,10 @@ def test_running_sum_handoff_chains(oracle, width, spp, monkeypatch):
     assert np.array_equal(out, ref) and st["rays"] == rays
 
 
-@pytest.mark.parametrize("n_big,ground,n_unbound", [(0, False, 0), (0, True, 0), (1, True, 0), (2, True, 0),
-                                                    (3, True, 0), (4, True, 0), (3, True, 2)])
-def test_always_list_sizes_bit_exact(oracle, n_big, ground, n_unbound):
-    """The always-list (rt_bvh.cpp: huge / big / unboundable spheres tested by every ray before the
-    walk) at every size the kernel distinguishes: 0 to 4 spheres take the unrolled path whose
-    geometry and original index come by scalar loads at immediate offsets from the kernarg
-    pointers; more than 4 (unboundable spheres beside the capped big ones) take the runtime loop.
-    A grid of small spheres with n_big radius-1.2 spheres among them (box area >= 10x the median:
-    big), an optional radius-1000 ground (huge) and n_unbound spheres centred at 2e30 (never hit,
-    but tested)."""
+def always_list_scene(n_big, ground, n_unbound):
+    """The scene and camera of test_always_list_sizes_bit_exact (64 x 42, 4 spp): a grid of small
+    spheres with n_big radius-1.2 spheres among them, an optional radius-1000 ground and n_unbound
+    spheres centred at 2e30."""
     rng = np.random.default_rng(100 + 10 * n_big + n_unbound + (5 if ground else 0))
     sph = []
     for a in range(-4, 4):
@@ -550,9 +544,35 @@ def test_always_list_sizes_bit_exact(oracle, n_big, ground, n_unbound):
     scene.world = arr
     cam = (rtzig.Camera.builder(64, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10.0)
            .setViewport((13, 2, 3), (0, 0, 0), 20.0).setSamplesPerPixel(4).build())
+    return arr, cam
+
+
+@pytest.mark.parametrize("n_big,ground,n_unbound", [(0, False, 0), (0, True, 0), (1, True, 0), (2, True, 0),
+                                                    (3, True, 0), (4, True, 0), (3, True, 2)])
+def test_always_list_sizes_bit_exact(oracle, n_big, ground, n_unbound):
+    """The always-list (rt_bvh.cpp: huge / big / unboundable spheres tested by every ray before the
+    walk) at every size the kernel distinguishes: 0 to 4 spheres take the unrolled path whose
+    geometry and original index come by scalar loads at immediate offsets from the kernarg
+    pointers; more than 4 (unboundable spheres beside the capped big ones) take the runtime loop.
+    A grid of small spheres with n_big radius-1.2 spheres among them (box area >= 10x the median:
+    big), an optional radius-1000 ground (huge) and n_unbound spheres centred at 2e30 (never hit,
+    but tested)."""
+    arr, cam = always_list_scene(n_big, ground, n_unbound)
     out, st = gpu_render(cam, arr, n_gpus=1)
     ref, rays = oracle.render_b(cam.cam, arr, threads=8)
     assert np.array_equal(out, ref) and st["rays"] == rays
+
+
+def far_origin_scene(width=96):
+    """The scene and camera of test_far_origin_lanes_walk_without_culling: the final scene of seed
+    0xfa7 plus an unboundable radius-2e30 metal sphere."""
+    scene = rtzig.Scene.init(0xfa7).generateWorld()
+    huge = RtSphere(center=D3(0, -2e30, 0), radius=2e30, material=RT_METAL, albedo=D3(0.7, 0.7, 0.7), fuzz=0.3)
+    arr = (RtSphere * (len(scene.world) + 1))(*scene.world, huge)
+    scene.world = arr
+    cam = (rtzig.Camera.builder(width, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10)
+           .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(4).build())
+    return arr, cam
 
 
 @pytest.mark.parametrize("scale", [None, "0.0", "0.05"])
@@ -565,12 +585,7 @@ def test_far_origin_lanes_walk_without_culling(oracle, monkeypatch, scale):
     monkeypatch.setenv("RTZIG_KERNEL", "bvh")
     if scale is not None:
         monkeypatch.setenv("RTZIG_BVH_ORIGIN_SCALE", scale)
-    scene = rtzig.Scene.init(0xfa7).generateWorld()
-    huge = RtSphere(center=D3(0, -2e30, 0), radius=2e30, material=RT_METAL, albedo=D3(0.7, 0.7, 0.7), fuzz=0.3)
-    arr = (RtSphere * (len(scene.world) + 1))(*scene.world, huge)
-    scene.world = arr
-    cam = (rtzig.Camera.builder(96, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10)
-           .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(4).build())
+    arr, cam = far_origin_scene()
     out, st = gpu_render(cam, arr, n_gpus=1)
     ref, rays = oracle.render_b(cam.cam, arr, threads=16)
     assert np.array_equal(out, ref) and st["rays"] == rays

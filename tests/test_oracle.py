@@ -82,6 +82,26 @@ def test_color_kat(oracle):
     assert rgb.tolist() == [[255, 0, 255], [0, 255, 255]]
 
 
+def test_color_byte_boundaries_need_a_correctly_rounded_sqrt(oracle):
+    """Byte k starts at (k/256)^2.  The neighbour just below it rounds back up to k/256 under a
+    correctly rounded sqrt for 102 of the 255 boundaries and stays at byte k - 1 for the other 153:
+    these inputs tell a sqrt that is one ulp off (tests/domain_values.py feeds them to the device)."""
+    import domain_values as dv
+    k = np.arange(1, 256)
+    sq = (k / 256.0) ** 2
+    byte = lambda x: oracle.to_rgb8(np.stack([x, x, x], 1))[:, 0]
+    assert np.array_equal(byte(sq), k) and np.array_equal(byte(np.nextafter(sq, 2.0)), k)
+    below = byte(np.nextafter(sq, 0.0))
+    assert int((below == k).sum()) == 102 and int((below == k - 1).sum()) == 153
+    assert np.array_equal(below == k, np.sqrt(np.nextafter(sq, 0.0)) == k / 256.0)
+    x = 0.999 * 0.999  # the clamp's corner: 256 * 0.999 = 255.744
+    assert byte(np.array([np.nextafter(x, 0.0), x, np.nextafter(x, 2.0), 1.0, 1.5, np.inf])).tolist() == [255] * 6
+    assert byte(np.array([0.0, -0.0, -0.3, 5e-324, 1e-320, np.nan])).tolist() == [0] * 6
+    import rtzig
+    a = dv.pixels(len(dv.channel_values()))
+    assert np.array_equal(rtzig.to_rgb8(a), oracle.to_rgb8(a))  # the product's host Color.toRgb too
+
+
 def _sphere(center, radius, kind=RT_LAMBERTIAN, albedo=(1, 1, 1), fuzz=0.0, ior=1.0):
     return RtSphere(center=D3(*center), radius=radius, material=kind, albedo=D3(*albedo),
                     fuzz=fuzz, refraction_index=ior)
@@ -204,6 +224,47 @@ def test_presets_statistically_match_reference_images(oracle, golden_dir, config
     floor = _box_rmse(A, B)
     assert np.abs(B.astype(np.float64).mean(axis=(0, 1)) - gold.astype(np.float64).mean(axis=(0, 1))).max() <= 1.0
     assert _box_rmse(B, gold) <= 1.5 * floor, (_box_rmse(B, gold), floor)
+
+
+# ---- oracle_accumulate_b: a sample range added onto stored sums ----------------------------------
+def _cam37(spp, oracle):
+    return oracle.camera_build(golden_params(width=37, spp=spp))
+
+
+@pytest.mark.parametrize("split", [[12], [1, 11], [5, 7], [4, 1, 7], [3] * 4], ids=lambda s: "-".join(map(str, s)))
+def test_accumulate_b_chained_splits_equal_render_b(oracle, split):
+    """Chained calls over any split of [0, n), scaled once by 1.0 / n, have the bits of oracle_render_b
+    at spp = n (camera.zig:133-137: samples added in order, one scale), and the calls' rays sum to its."""
+    spheres, _ = oracle.scene_final(0xDEADBEEF)
+    n = sum(split)
+    cam = _cam37(n, oracle)
+    ref, ref_rays = oracle.render_b(cam, spheres, threads=8)
+    sums, rays, done = None, 0, 0
+    for count in split:
+        sums, r = oracle.accumulate_b(cam, spheres, done, count, sums, threads=8)
+        rays += r
+        done += count
+    assert np.array_equal(sums * (1.0 / n), ref)
+    assert rays == ref_rays
+    # a row subset, and a thread count that must not matter
+    sub, _ = oracle.accumulate_b(cam, spheres, 0, n, row0=1, row_step=3, n_rows=6, threads=1)
+    assert np.array_equal(sub * (1.0 / n), ref[1:19:3])
+
+
+def test_accumulate_b_keys_with_the_64_bit_sample_number(oracle):
+    """A range that ends at 2^32 - 1 differs from the one 2^31 lower (bit 31 of the sample number
+    reaches the key), and the additions start from `sums`."""
+    spheres, _ = oracle.scene_final(0xDEADBEEF)
+    cam = _cam37(1, oracle)
+    k = 5
+    hi, _ = oracle.accumulate_b(cam, spheres, 2 ** 32 - 1 - k, k, threads=8)
+    lo, _ = oracle.accumulate_b(cam, spheres, 2 ** 31 - 1 - k, k, threads=8)
+    assert np.isfinite(hi).all() and np.isfinite(lo).all()
+    assert (hi != lo).any(axis=-1).mean() > 0.9
+    first, _ = oracle.accumulate_b(cam, spheres, 0, 1, threads=8)
+    seeded = np.full((20, 37, 3), 0.375)
+    got, _ = oracle.accumulate_b(cam, spheres, 0, 1, seeded, threads=8)
+    assert np.array_equal(got, 0.375 + first) and (seeded == 0.375).all()
 
 
 # ---- oracle mode F: the per-sample reference of the f32 fast mode (DESIGN.md §5.6) ---------------
