@@ -328,6 +328,29 @@ struct BvhArgs {
 __host__ __device__ inline uint32_t bvh_leaves_offset(uint32_t n_nodes) {
     return (n_nodes * (uint32_t)sizeof(BvhNode) + 15u) & ~15u;
 }
+// The one rule for "does the tree go to LDS", for a block of `block` threads whose tree + stacks may
+// take `budget` bytes (kLdsSceneBudget, or kLdsSceneBudgetProf for the instrumented block): every BVH
+// launcher sizes its dynamic LDS from it, and the host rejects a trained tree by it (rt_scene.cpp).
+struct LdsPlan {
+    bool lds_scene;      // tree + stacks fit: the tree is staged in LDS
+    size_t scene_bytes;  // [nodes, padded to 16 B][leaves]
+    size_t stack_bytes;  // stack_depth x block entries: StackEntry beside an LDS tree, else int32
+};
+inline LdsPlan bvh_lds_plan(uint32_t n_nodes, uint32_t n_leaves, uint32_t stack_depth, uint32_t block, size_t budget) {
+    const size_t leaf_bytes = (size_t)n_leaves * sizeof(BvhLeaf);
+    const size_t scene_bytes = (size_t)bvh_leaves_offset(n_nodes) + leaf_bytes;
+    // int16 stack entries (RTZIG_STACK16) hold node and leaf byte offsets below 2^15
+    const bool refs16 = bvh_leaves_offset(n_nodes) < 32768u && leaf_bytes < 32768u;
+    const size_t lds_entry = refs16 ? sizeof(StackEntry) : sizeof(int32_t);
+    const bool lds_scene = (size_t)stack_depth * block * lds_entry + scene_bytes <= budget &&
+                           (sizeof(StackEntry) == sizeof(int32_t) || refs16);
+    return {lds_scene, scene_bytes, (size_t)stack_depth * block * (lds_scene ? sizeof(StackEntry) : sizeof(int32_t))};
+}
+// Dynamic LDS of the list-walk kernels: the padded geometry (the lds variants), then the block's seed
+// windows where the kernel has them
+inline size_t list_walk_lds(bool lds_geo, uint32_t n_pad, bool seed_win) {
+    return (lds_geo ? (size_t)n_pad * sizeof(GeoRec) : 0) + (seed_win && kSeedWin ? (kBlock / 64) * kSeedWinBytes : 0);
+}
 
 }  // namespace rtk
 

@@ -2661,7 +2661,7 @@ extern "C" hipError_t rtk_launch_samples(const rtk::KernelParams* p, const rtk::
     const uint64_t total = (uint64_t)p->n_rows * p->width * p->s_count;
     if (total == 0) return hipSuccess;
     const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
-    const size_t shmem = (v.lds ? (size_t)p->n_pad * sizeof(GeoRec) : 0) + (kSeedWin ? (kBlock / 64) * kSeedWinBytes : 0);
+    const size_t shmem = list_walk_lds(v.lds, p->n_pad, true);
     const uint64_t need = (total + kBlock - 1) / kBlock;
     auto* st = (unsigned long long*)stats;
     if (name) *name = v.name;
@@ -2686,15 +2686,9 @@ hipError_t launch_bvh(const rtk::KernelParams* p, const rtk::BvhArgs* b, const r
     if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
     const bool prof = p->prof != 0;
     const uint32_t block = (uint32_t)bvh_block(prof);
-    const size_t scene_bytes = (size_t)bvh_leaves_offset(b->n_nodes) + (size_t)b->n_leaves * sizeof(BvhLeaf);
-    // int16 stack entries (RTZIG_STACK16) hold node and leaf byte offsets below 2^15
-    const bool refs16 = bvh_leaves_offset(b->n_nodes) < 32768u && (size_t)b->n_leaves * sizeof(BvhLeaf) < 32768u;
-    const size_t lds_entry = refs16 ? sizeof(StackEntry) : sizeof(int32_t);
     // scene in LDS when the block's share of a CU holds tree + stacks + seed windows (kLdsSceneBudget)
-    const bool lds_scene = (size_t)b->stack_depth * block * lds_entry + scene_bytes <=
-                               (prof ? kLdsSceneBudgetProf : kLdsSceneBudget) &&
-                           (sizeof(StackEntry) == sizeof(int32_t) || refs16);
-    const size_t stack_bytes = (size_t)b->stack_depth * block * (lds_scene ? sizeof(StackEntry) : sizeof(int32_t));
+    const auto [lds_scene, scene_bytes, stack_bytes] =
+        bvh_lds_plan(b->n_nodes, b->n_leaves, b->stack_depth, block, prof ? kLdsSceneBudgetProf : kLdsSceneBudget);
     // + the waves' seed windows (kSeedWin, the f64 kernel with the tree in LDS), 16-B aligned after the stacks
     const size_t shmem = (((lds_scene ? scene_bytes : 0) + stack_bytes + 15) & ~(size_t)15) +
                          (!lds_scene ? 0 : (prof ? kSeedWinProfBytes : kSeedWinBlockBytes));
@@ -2762,7 +2756,7 @@ extern "C" hipError_t rtk_launch_gather(const rtk::KernelParams* p, const rtk::B
     if (b == nullptr) {
         if (fast) return hipErrorInvalidValue;  // fast mode walks the tree
         const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
-        const size_t shmem = (v.lds ? (size_t)p->n_pad * sizeof(GeoRec) : 0) + (kSeedWin ? (kBlock / 64) * kSeedWinBytes : 0);
+        const size_t shmem = list_walk_lds(v.lds, p->n_pad, true);
         const uint64_t need = (total + kBlock - 1) / kBlock;
         auto launch = [&](auto kernel, const char* nm) -> hipError_t {
             const uint32_t blocks = grid_blocks(need, persistent_blocks(kernel, shmem), ua, kBlock);
@@ -2775,12 +2769,7 @@ extern "C" hipError_t rtk_launch_gather(const rtk::KernelParams* p, const rtk::B
     if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
     // the LDS shape of launch_bvh's uninstrumented kernels
     const uint32_t block = (uint32_t)kBlockBvh;
-    const size_t scene_bytes = (size_t)bvh_leaves_offset(b->n_nodes) + (size_t)b->n_leaves * sizeof(BvhLeaf);
-    const bool refs16 = bvh_leaves_offset(b->n_nodes) < 32768u && (size_t)b->n_leaves * sizeof(BvhLeaf) < 32768u;
-    const size_t lds_entry = refs16 ? sizeof(StackEntry) : sizeof(int32_t);
-    const bool lds_scene = (size_t)b->stack_depth * block * lds_entry + scene_bytes <= kLdsSceneBudget &&
-                           (sizeof(StackEntry) == sizeof(int32_t) || refs16);
-    const size_t stack_bytes = (size_t)b->stack_depth * block * (lds_scene ? sizeof(StackEntry) : sizeof(int32_t));
+    const auto [lds_scene, scene_bytes, stack_bytes] = bvh_lds_plan(b->n_nodes, b->n_leaves, b->stack_depth, block, kLdsSceneBudget);
     const size_t shmem = (((lds_scene ? scene_bytes : 0) + stack_bytes + 15) & ~(size_t)15) + (!lds_scene ? 0 : kSeedWinBlockBytes);
     const uint64_t need = (total + block - 1) / block;
     auto launch = [&](auto kernel, const char* nm) -> hipError_t {
@@ -2837,7 +2826,7 @@ extern "C" hipError_t rtk_launch_features(const rtk::KernelParams* p, const rtk:
     };
     if (b == nullptr) {
         const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
-        const size_t shmem = v.lds ? (size_t)p->n_pad * sizeof(GeoRec) : 0;
+        const size_t shmem = list_walk_lds(v.lds, p->n_pad, false);  // the feature kernels have no seed window
         auto launch = [&](auto kernel, const char* nm) -> hipError_t {
             const uint64_t cap = persistent_blocks(kernel, shmem);
             const uint64_t need = ((uint64_t)f.n_tiles + kBlock / 64 - 1) / (kBlock / 64);
@@ -2857,12 +2846,7 @@ extern "C" hipError_t rtk_launch_features(const rtk::KernelParams* p, const rtk:
     if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
     // the tree goes to LDS exactly when launch_bvh's uninstrumented kernels hold it there
     const uint32_t block = (uint32_t)kBlockBvh;
-    const size_t scene_bytes = (size_t)bvh_leaves_offset(b->n_nodes) + (size_t)b->n_leaves * sizeof(BvhLeaf);
-    const bool refs16 = bvh_leaves_offset(b->n_nodes) < 32768u && (size_t)b->n_leaves * sizeof(BvhLeaf) < 32768u;
-    const size_t lds_entry = refs16 ? sizeof(StackEntry) : sizeof(int32_t);
-    const bool lds_scene = (size_t)b->stack_depth * block * lds_entry + scene_bytes <= kLdsSceneBudget &&
-                           (sizeof(StackEntry) == sizeof(int32_t) || refs16);
-    const size_t stack_bytes = (size_t)b->stack_depth * block * (lds_scene ? sizeof(StackEntry) : sizeof(int32_t));
+    const auto [lds_scene, scene_bytes, stack_bytes] = bvh_lds_plan(b->n_nodes, b->n_leaves, b->stack_depth, block, kLdsSceneBudget);
     const size_t shmem = (lds_scene ? scene_bytes : 0) + stack_bytes;
     auto launch = [&](auto kernel, const char* nm) -> hipError_t {
         uint32_t cap32 = 0;

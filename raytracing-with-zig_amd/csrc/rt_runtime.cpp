@@ -29,55 +29,26 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/rt.h"
-#include "rt_bvh.hpp"
 #include "rt_denoise.h"
-#include "rt_device.h"
 #include "rt_kernel.h"
+#include "rt_scene.hpp"
 #include "rt_schedule.hpp"
 #include "rt_temporal.h"
 
 void rt_set_last_error(const std::string& msg);
 
+using namespace rtscene;  // the host scene and its tree (rt_scene.hpp)
+
 namespace {
 
 constexpr uint32_t kMaxTimed = 1024;  // event-pool bound of rt_context_kernel_times_total
 constexpr size_t kEventsPerCall = 4;   // timed call: start, sample kernel done, reduce start, reduce done
-
-// Host-side scene: device records of the Hittable list plus its BVH, built once per sphere list and
-// uploaded to every device that renders it.
-struct SceneData {
-    std::vector<rt_sphere> spheres;
-    std::vector<rtk::GeoRec> geo;  // padded to kPad with never-hit sentinels
-    std::vector<rtk::MatRec> mat;
-    bool bvh_ok = false;
-    double origin_bound = 0;
-    std::vector<rtk::BvhNode> nodes;
-    std::vector<rtk::BvhLeaf> leaves;
-    std::vector<rtk::GeoRec> ageo;
-    std::vector<uint32_t> asid;
-    uint32_t n_nodes = 0, n_leaves = 0, n_always = 0, depth = 0;
-    bool trained = false;      // the tree was built from sample rays of camera `view` (train_bvh)
-    bool train_tried = false;  // train_bvh ran for `view` (trained or not: a failure is not retried)
-    rt_camera view{};
-};
-
-// Ray-driven tree (rtbvh::build with sample rays): trained for launches of at least
-// kTrainMinSamples samples on scenes of at least kTrainMinSpheres spheres, from the paths of
-// kTrainSamples camera samples.  Config 4: node visits per ray 6.97 -> 6.2.
-constexpr uint64_t kTrainMinSamples = 1ull << 25;
-constexpr size_t kTrainMinSpheres = 32;
-#ifndef RTZIG_TRAIN_SAMPLES
-#define RTZIG_TRAIN_SAMPLES 6000
-#endif
-constexpr size_t kTrainSamples = RTZIG_TRAIN_SAMPLES;  // build knob
-constexpr uint64_t kTrainSeed = 0x7261792d74726565ull;
 constexpr uint32_t kLinearMaxSpheres = 8;    // scenes this small walk the list (use_bvh)
 constexpr const char* kStallMsg =
     "render kernel: a wave gave up waiting for a running-sum hand-off (one wait exceeded its bound: 40 s, "
@@ -184,7 +155,7 @@ struct rt_context {
     bool timing = false;
     bool profile = false;  // instrumented kernels: d_stats must hold RT_PROFILE_STATS_WORDS uint64 (rt.h)
     int precision = RT_PRECISION_F64;
-    std::vector<hipEvent_t> events;  // 3 per timed call: start, sample kernel done, reduce done
+    std::vector<hipEvent_t> events;  // kEventsPerCall per timed slot (open_call)
     uint32_t call_first = 0;
     uint32_t timed_calls = 0;
     uint32_t log_used = 0;
@@ -253,215 +224,22 @@ int validate_spheres(const rt_sphere* s, size_t n) {
     return RT_OK;
 }
 
-// Builder ref (node index >= 0, ~leaf index < 0) -> device ref (byte offsets, see build_bvh).
-int32_t device_ref(int32_t ref) {
-    if (ref >= 0) return (int32_t)((int64_t)ref * (int64_t)sizeof(rtk::BvhNode));
-    return ~(int32_t)((int64_t)(~ref) * (int64_t)sizeof(rtk::BvhLeaf));
+// The ordering events of a call (rt_context "ordering"), each recorded with its bookkeeping.
+int record_launched(rt_context* ctx, hipStream_t s) {
+    HIP_CHECK(hipEventRecord(ctx->launched, s));
+    ctx->launched_valid = true;
+    ctx->launched_stream = s;
+    return RT_OK;
 }
-
-rtk::GeoRec geo_of(const rt_sphere* s) {
-    rtk::GeoRec g;
-    if (!s) {  // never-hit sentinel (rt_kernel.h)
-        g.cx = g.cy = g.cz = 0.0;
-        g.r2 = -std::numeric_limits<double>::infinity();
-        return g;
-    }
-    const double r = s->radius > 0 ? s->radius : 0.0;  // Sphere.init clamps (sphere.zig:21)
-    g.cx = s->center[0];
-    g.cy = s->center[1];
-    g.cz = s->center[2];
-    g.r2 = r * r;
-    return g;
+int record_reduced(rt_context* ctx, uint32_t buf, hipStream_t s) {
+    HIP_CHECK(hipEventRecord(ctx->reduced[buf], s));
+    ctx->reduced_valid[buf] = true;
+    return RT_OK;
 }
-
-// Sets sd's device tree from `bvh` (built for ray origins with |o_i| <= bound; rt_kernel.h layout).
-void set_tree(SceneData& sd, const rtbvh::Bvh& bvh, double bound) {
-    sd.trained = false;
-    sd.train_tried = false;
-    // byte-offset refs must fit int32 (and stay clear of the walk's INT32_MIN "done" marker)
-    const bool fits = bvh.nodes.size() * sizeof(rtk::BvhNode) < (1ull << 30) &&
-                      bvh.slot_to_sphere.size() / rtk::kLeafBvh * sizeof(rtk::BvhLeaf) < (1ull << 30);
-    sd.bvh_ok = bvh.ok && fits;
-    sd.origin_bound = bound;
-    if (!sd.bvh_ok) return;
-    static_assert(rtbvh::kLeafMax == rtk::kLeafBvh && rtbvh::kMaxDepth == rtk::kMaxDepthBvh, "BVH constants differ");
-    const size_t nn = bvh.nodes.size();
-    const size_t na = bvh.n_always;
-    const size_t nl = (bvh.slot_to_sphere.size() - na) / rtk::kLeafBvh;
-    auto sphere = [&](uint32_t k) { return k == rtbvh::kSentinel ? nullptr : &sd.spheres[k]; };
-    sd.nodes.assign(nn, rtk::BvhNode{});
-    for (size_t i = 0; i < nn; i++) {
-        const rtbvh::Node& src = bvh.nodes[i];
-        rtk::BvhNode& d = sd.nodes[i];
-        for (int a = 0; a < 3; a++) {  // {lo, hi, hi, lo}: see rtk::BvhNode
-            d.c0[a][0] = d.c0[a][3] = src.lo0[a];
-            d.c0[a][1] = d.c0[a][2] = src.hi0[a];
-            d.c1[a][0] = d.c1[a][3] = src.lo1[a];
-            d.c1[a][1] = d.c1[a][2] = src.hi1[a];
-        }
-        // device refs are BYTE offsets (node: ref * 104 >= 0, leaf: ~(leaf * sizeof(BvhLeaf))) so the
-        // walk forms LDS/global addresses with an add instead of a quarter-rate v_mul_lo_u32
-        d.ref0 = device_ref(src.ref0);
-        d.ref1 = device_ref(src.ref1);
-    }
-    sd.leaves.assign(nl ? nl : 1, rtk::BvhLeaf{});
-    for (size_t l = 0; l < nl; l++)
-        for (int u = 0; u < rtk::kLeafBvh; u++) {
-            const uint32_t k = bvh.slot_to_sphere[na + l * rtk::kLeafBvh + u];
-            const rtk::GeoRec g = geo_of(sphere(k));
-            sd.leaves[l].g[u] = rtk::LeafGeo{g.cx, g.cy, g.cz, g.r2};
-            sd.leaves[l].sid[u] = k;
-        }
-    sd.ageo.assign(na ? na : 1, geo_of(nullptr));
-    sd.asid.assign(na ? na : 1, 0);
-    for (size_t q = 0; q < na; q++) {
-        sd.ageo[q] = geo_of(sphere(bvh.slot_to_sphere[q]));
-        sd.asid[q] = bvh.slot_to_sphere[q];
-    }
-    sd.n_nodes = (uint32_t)nn;
-    sd.n_leaves = (uint32_t)nl;
-    sd.n_always = (uint32_t)na;
-    sd.depth = (uint32_t)std::max(2, std::min(bvh.depth, rtk::kMaxDepthBvh));
-}
-
-// The SAH BVH of sd.spheres, valid for ray origins with |o_i| <= bound.
-void build_bvh(SceneData& sd, double bound) {
-    rtbvh::Bvh bvh;  // ok = false: the linear walk
-    try {            // the builder uses host threads for the top of the tree
-        bvh = rtbvh::build(sd.spheres.data(), sd.spheres.size(), bound);
-    } catch (const std::exception&) {
-        bvh = rtbvh::Bvh{};
-    }
-    set_tree(sd, bvh, bound);
-}
-
-// Do two cameras shoot the same rays (every field getRay / rayColor read except spp and seed)?
-bool same_view(const rt_camera& a, const rt_camera& b) {
-    rt_camera x = a, y = b;
-    x.samples_per_pixel = y.samples_per_pixel = 0;
-    x.pixel_samples_scale = y.pixel_samples_scale = 0;
-    x.seed = y.seed = 0;
-    return std::memcmp(&x, &y, sizeof x) == 0;
-}
-
-// Should a launch of `samples` samples train the tree for its camera?  RTZIG_BVH_TRAIN=0|1 forces
-// it off / on (test hook: trained trees on small launches).
-bool want_train(const SceneData& sd, uint64_t samples) {
-    if (const char* e = std::getenv("RTZIG_BVH_TRAIN")) {
-        if (std::strcmp(e, "0") == 0) return false;
-        if (std::strcmp(e, "1") == 0) return sd.bvh_ok;
-    }
-    return sd.bvh_ok && samples >= kTrainMinSamples && sd.spheres.size() >= kTrainMinSpheres;
-}
-
-// Rebuilds sd's tree from sample rays of `cam` (rtbvh::sample_rays over the SAH tree, then the
-// ray-driven build).  The result depends only on (spheres, origin bound, view), so it is memoised
-// process-wide: rt_render's devices and later calls reuse it.  Any valid tree returns the same
-// bits (rt_bvh.hpp); this one only visits fewer nodes for this camera's rays.  A training that
-// fails or is rejected (builder exception, no tree, LDS budget) keeps the current tree and is
-// memoised too (train_tried), so later launches of the same view do not quiesce and retry it.
-bool try_train(SceneData& sd, const rt_camera& cam) {
-    const double bound = sd.origin_bound;
-    rtbvh::Bvh sah, tree;
-    try {  // the trained build runs on host threads; if they cannot be had, keep the current tree
-        sah = rtbvh::build(sd.spheres.data(), sd.spheres.size(), bound);
-        if (!sah.ok) return false;
-        const std::vector<rtbvh::TrainRay> rays =
-            rtbvh::sample_rays(sd.spheres.data(), sd.spheres.size(), cam, sah, kTrainSamples, kTrainSeed);
-        tree = rtbvh::build(sd.spheres.data(), sd.spheres.size(), bound, &rays);
-    } catch (const std::exception&) {
-        return false;
-    }
-    if (!tree.ok) return false;
-    // the kernel stages the tree in LDS when tree + stacks fit a block's 80 KiB (rt_kernel.hip); a
-    // trained tree that would not fit where the SAH tree does (or does not build) is not used
-    auto lds_bytes = [](const SceneData& t) {
-        return (size_t)rtk::bvh_leaves_offset(t.n_nodes) + (size_t)t.n_leaves * sizeof(rtk::BvhLeaf) +
-               (size_t)t.depth * rtk::kBlockBvh * sizeof(rtk::StackEntry);
-    };
-    SceneData sah_sd = sd;
-    set_tree(sah_sd, sah, bound);
-    SceneData tr = sd;
-    set_tree(tr, tree, bound);
-    if (!tr.bvh_ok || (lds_bytes(tr) > rtk::kLdsSceneBudget && lds_bytes(sah_sd) <= rtk::kLdsSceneBudget)) {
-        if (sah_sd.bvh_ok) sd = sah_sd;
-        return false;
-    }
-    sd = tr;
-    return true;
-}
-
-// The tree preparation a launch of `samples` samples with camera `cam` does before it runs
-// (render_rows): a rebuild with a larger origin bound when the camera's ray origins lie beyond it,
-// then the ray-driven training.  Host work only; rt_render runs it on a host thread while the HIP
-// runtime and the contexts initialise, so render_rows finds nothing left to do.
-double cam_origin_bound(const rt_camera& cam) {
-    double b = 0;
-    for (int a = 0; a < 3; a++)
-        b = std::max(b, std::fabs(cam.center[a]) + std::fabs(cam.defocus_disk_u[a]) + std::fabs(cam.defocus_disk_v[a]));
-    return b;
-}
-bool needs_far_rebuild(const SceneData& sd, const rt_camera& cam) {
-    return sd.bvh_ok && !(cam_origin_bound(cam) <= sd.origin_bound);
-}
-double far_bound(const SceneData& sd, const rt_camera& cam) {
-    return std::max(cam_origin_bound(cam), sd.origin_bound) * 1.01;
-}
-bool needs_training(const SceneData& sd, const rt_camera& cam, uint64_t samples) {
-    return want_train(sd, samples) && !(sd.train_tried && same_view(sd.view, cam));
-}
-void train_bvh(SceneData& sd, const rt_camera& cam);
-
-void train_bvh(SceneData& sd, const rt_camera& cam) {
-    static std::mutex mu;
-    static SceneData memo;
-    static bool memo_valid = false;
-    std::lock_guard<std::mutex> lock(mu);
-    if (memo_valid && same_view(memo.view, cam) && memo.origin_bound == sd.origin_bound &&
-        memo.spheres.size() == sd.spheres.size() &&
-        std::memcmp(memo.spheres.data(), sd.spheres.data(), sd.spheres.size() * sizeof(rt_sphere)) == 0) {
-        sd = memo;
-        return;
-    }
-    const bool ok = try_train(sd, cam);
-    sd.trained = ok;
-    sd.train_tried = true;
-    sd.view = cam;
-    memo = sd;
-    memo_valid = true;
-}
-
-// Device records + BVH of a sphere list (validated by the caller).
-void build_scene(const rt_sphere* spheres, size_t n, SceneData& sd) {
-    sd = SceneData{};
-    sd.spheres.assign(spheres, spheres + n);
-    const size_t n_pad = (n + rtk::kPad - 1) / rtk::kPad * rtk::kPad;
-    sd.geo.assign(n_pad, geo_of(nullptr));
-    sd.mat.assign(n, rtk::MatRec{});
-    for (size_t k = 0; k < n; k++) {
-        sd.geo[k] = geo_of(&spheres[k]);
-        rtk::MatRec& m = sd.mat[k];
-        const double r = spheres[k].radius > 0 ? spheres[k].radius : 0.0;
-        for (int c = 0; c < 3; c++) m.albedo[c] = spheres[k].albedo[c];
-        m.fuzz = spheres[k].fuzz;
-        m.ior = spheres[k].refraction_index;
-        m.inv_r = 1.0 / r;
-        const double ior = spheres[k].refraction_index;
-        m.inv_ior = 1.0 / ior;
-        for (int face = 0; face < 2; face++) {  // reflectance()'s r0 (material.zig:106-108) per face
-            const double ri = face == 0 ? m.inv_ior : ior;
-            double r0 = (1 - ri) / (1 + ri);
-            r0 = r0 * r0;
-            (face == 0 ? m.r0_front : m.r0_back) = r0;
-        }
-        m.kind = spheres[k].material;
-    }
-    const double extent = rtbvh::scene_extent(spheres, n);
-    build_bvh(sd, extent * (1.0 + 0x1p-20) + 1e-300);
-}
-
-bool same_spheres(const SceneData& sd, const rt_sphere* s, size_t n) {
-    return sd.spheres.size() == n && n && std::memcmp(sd.spheres.data(), s, n * sizeof(rt_sphere)) == 0;
+int record_done(rt_context* ctx, hipStream_t s) {
+    HIP_CHECK(hipEventRecord(ctx->done, s));
+    ctx->done_valid = true;
+    return RT_OK;
 }
 
 // Runs a deferred call's pending reduce pass whole, on the stream its output was promised on, after
@@ -475,11 +253,8 @@ int flush_fold(rt_context* ctx, bool own_stream = false) {
     if (ctx->launched_valid) HIP_CHECK(hipStreamWaitEvent(fs, ctx->launched, 0));
     HIP_CHECK(hipMemsetAsync(ctx->fold.ctr, 0, sizeof(unsigned long long), fs));
     HIP_CHECK(rtk_launch_fold_rest(&ctx->fold, fs));
-    HIP_CHECK(hipEventRecord(ctx->reduced[ctx->fold_buf], fs));
-    ctx->reduced_valid[ctx->fold_buf] = true;
-    HIP_CHECK(hipEventRecord(ctx->done, fs));
-    ctx->done_valid = true;
-    return RT_OK;
+    const int rc = record_reduced(ctx, ctx->fold_buf, fs);
+    return rc ? rc : record_done(ctx, fs);
 }
 
 // Waits until the device has finished the context's last render (before rewriting its buffers); a
@@ -510,19 +285,6 @@ int ensure_buffer(rt_context* ctx, void** ptr, size_t* bytes, size_t need) {
     return RT_OK;
 }
 
-// ensure_buffer that also gives memory back: a buffer more than 25% larger than `need` (held for
-// an earlier, larger launch or a kernel with more resident waves) is reallocated at `need`
-int fit_buffer(rt_context* ctx, void** ptr, size_t* bytes, size_t need) {
-    if (*ptr && *bytes > need + need / 4) {
-        int rc = quiesce(ctx);
-        if (rc) return rc;
-        (void)hipFree(*ptr);
-        *ptr = nullptr;
-        *bytes = 0;
-    }
-    return ensure_buffer(ctx, ptr, bytes, need);
-}
-
 // Frees a workspace buffer the current launch's mode does not use (after the last render).
 int release_buffer(rt_context* ctx, void** ptr, size_t* bytes) {
     if (!*ptr) return RT_OK;
@@ -532,6 +294,16 @@ int release_buffer(rt_context* ctx, void** ptr, size_t* bytes) {
     *ptr = nullptr;
     *bytes = 0;
     return RT_OK;
+}
+
+// ensure_buffer that also gives memory back: a buffer more than 25% larger than `need` (held for
+// an earlier, larger launch or a kernel with more resident waves) is reallocated at `need`
+int fit_buffer(rt_context* ctx, void** ptr, size_t* bytes, size_t need) {
+    if (*ptr && *bytes > need + need / 4) {
+        const int rc = release_buffer(ctx, ptr, bytes);
+        if (rc) return rc;
+    }
+    return ensure_buffer(ctx, ptr, bytes, need);
 }
 
 template <class T>
@@ -716,6 +488,96 @@ hipError_t make_event(hipEvent_t* e, bool timed) {
     return timed ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming);
 }
 
+// ---- the launch protocol: what every call that launches on a context does around its kernels ----
+
+// Opens a call that launches on `s`.  With timing on it reserves n_slots slots of the event log (a
+// gather pass one per sub-pass, at most kMaxTimed; every other call one) and *ev points at the first
+// slot's kEventsPerCall events (slot k: *ev + kEventsPerCall * k, k < ctx->timed_calls); else *ev is
+// null.  Then a previous call on another stream is waited for: it may still run its sample kernel on
+// the context's counters, flags, ring, sums and planes, and `launched` / `done` are re-recorded by
+// close_call, so they must still cover it.
+int open_call(rt_context* ctx, hipStream_t s, uint32_t n_slots, hipEvent_t** ev) {
+    *ev = nullptr;
+    if (ctx->timing) {
+        n_slots = std::min(n_slots, kMaxTimed);
+        if (ctx->log_used + n_slots > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
+        ctx->call_first = ctx->log_used;
+        ctx->log_used += n_slots;
+        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
+            hipEvent_t e;
+            HIP_CHECK(make_event(&e, true));
+            ctx->events.push_back(e);
+        }
+        ctx->timed_calls = n_slots;
+        *ev = &ctx->events[kEventsPerCall * ctx->call_first];
+    }
+    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
+    return RT_OK;
+}
+
+// Closes a call whose kernels all ran on `s`.  ev != nullptr: the call had no reduce pass and is
+// reported as the sample kernel, so its slot gets an empty reduce interval.  reduced_buf >= 0: the
+// call's last pass read that per-sample buffer (the gather pass, which records its own slots).
+int close_call(rt_context* ctx, hipStream_t s, hipEvent_t* ev, int reduced_buf = -1) {
+    if (ev)
+        for (int k = 1; k <= 3; k++) HIP_CHECK(hipEventRecord(ev[k], s));
+    int rc = record_launched(ctx, s);
+    if (!rc && reduced_buf >= 0) rc = record_reduced(ctx, (uint32_t)reduced_buf, s);
+    return rc ? rc : record_done(ctx, s);
+}
+
+// The counters exist from the first launch on.  The sticky error word starts clear; launches zero
+// only the counters before it.  On the launch stream: a null-stream hipMemset is asynchronous and NOT
+// ordered with a non-blocking stream, so it could land mid-kernel and reset the claim counters.
+int ensure_counters(rt_context* ctx, hipStream_t s) {
+    if (ctx->d_ctr) return RT_OK;
+    size_t cb = 0;
+    const int rc = ensure_buffer(ctx, (void**)&ctx->d_ctr, &cb, rtk::kCtrBytes);
+    if (rc) return rc;
+    HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrBytes, s));
+    return RT_OK;
+}
+
+// The tree a launch of `samples` samples with camera `cam` walks (rt_scene.hpp).  Camera-ray origins
+// (center + defocus disk) must lie inside the BVH padding's origin bound (lanes outside it would walk
+// without culling: correct, but every camera ray would pay); large launches walk a tree trained on
+// this camera's rays (same bits, fewer node visits).  Either waits for the previous render, which
+// may still walk the old tree.
+int prepare_tree(rt_context* ctx, const rt_camera& cam, uint64_t samples) {
+    if (needs_far_rebuild(ctx->scene, cam)) {
+        int rc = quiesce(ctx);
+        if (rc) return rc;
+        build_bvh(ctx->scene, far_bound(ctx->scene, cam));
+        rc = upload_bvh(ctx);
+        if (rc) return rc;
+        trace_mark("bvh_rebuild_far_camera");
+    }
+    if (needs_training(ctx->scene, cam, samples)) {
+        int rc = quiesce(ctx);
+        if (rc) return rc;
+        trace_mark("wait_previous_render");
+        train_bvh(ctx->scene, cam);
+        trace_mark("bvh_train_host");
+        rc = upload_bvh(ctx);
+        if (rc) return rc;
+        trace_mark("bvh_upload");
+    }
+    return RT_OK;
+}
+
+int check_rows(const rt_camera* cam, uint32_t row0, uint32_t row_step, uint32_t n_rows) {
+    const uint64_t last_row = (uint64_t)row0 + (uint64_t)(n_rows - 1) * row_step;
+    if (last_row < cam->image_height) return RT_OK;
+    rt_set_last_error("row range exceeds image_height");
+    return RT_ERR_INVALID;
+}
+
+int check_sample_range(uint32_t begin, uint32_t count) {
+    if ((uint64_t)begin + count <= 0xffffffffull) return RT_OK;
+    rt_set_last_error("sample_begin + sample_count exceeds 2^32 - 1");
+    return RT_ERR_INVALID;
+}
+
 }  // namespace
 
 extern "C" {
@@ -838,35 +700,12 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
     if (n_rows == 0) return RT_OK;
     if (!d_out) { rt_set_last_error("null output"); return RT_ERR_INVALID; }
     if (row_step == 0) row_step = 1;
-    const uint64_t last_row = (uint64_t)row0 + (uint64_t)(n_rows - 1) * row_step;
-    if (last_row >= cam->image_height) {
-        rt_set_last_error("row range exceeds image_height");
-        return RT_ERR_INVALID;
-    }
+    rc = check_rows(cam, row0, row_step, n_rows);
+    if (rc) return rc;
     HIP_CHECK(hipSetDevice(ctx->device));
     if (os == s) split = defer = false;  // one stream: the plain call (os may be the null stream)
-
-    // camera-ray origins (center + defocus disk) must lie inside the BVH padding's origin bound
-    // (lanes outside it would walk without culling: correct, but every camera ray would pay)
-    if (needs_far_rebuild(ctx->scene, *cam)) {
-        rc = quiesce(ctx);  // the previous render may still walk the old tree
-        if (rc) return rc;
-        build_bvh(ctx->scene, far_bound(ctx->scene, *cam));
-        rc = upload_bvh(ctx);
-        if (rc) return rc;
-        trace_mark("bvh_rebuild_far_camera");
-    }
-    // large launches walk a tree trained on this camera's rays (same bits, fewer node visits)
-    if (needs_training(ctx->scene, *cam, (uint64_t)n_rows * cam->image_width * cam->samples_per_pixel)) {
-        rc = quiesce(ctx);  // the previous render may still walk the old tree
-        if (rc) return rc;
-        trace_mark("wait_previous_render");
-        train_bvh(ctx->scene, *cam);
-        trace_mark("bvh_train_host");
-        rc = upload_bvh(ctx);
-        if (rc) return rc;
-        trace_mark("bvh_upload");
-    }
+    rc = prepare_tree(ctx, *cam, (uint64_t)n_rows * cam->image_width * cam->samples_per_pixel);
+    if (rc) return rc;
 
     const uint64_t P = (uint64_t)n_rows * cam->image_width;
     rtk::UnitArgs ua;
@@ -968,14 +807,7 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
         size_t fb = 0;
         rc = ensure_buffer(ctx, (void**)&ctx->d_fold_ctr, &fb, 2 * 16 * sizeof(unsigned long long));
     }
-    if (!rc && !ctx->d_ctr) {
-        size_t cb = 0;
-        rc = ensure_buffer(ctx, (void**)&ctx->d_ctr, &cb, rtk::kCtrBytes);
-        // the sticky error word starts clear; launches zero only the counters before it.  On the
-        // launch stream: a null-stream hipMemset is asynchronous and NOT ordered with this
-        // non-blocking stream, so it could land mid-kernel and reset the claim counters.
-        if (!rc) HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrBytes, s));
-    }
+    if (!rc) rc = ensure_counters(ctx, s);
     if (rc) return rc;
     trace_mark("workspace_alloc");
     ua.ring = direct ? nullptr : ctx->d_ring;
@@ -1005,21 +837,11 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
     }
     ua.scale = cam->pixel_samples_scale;
 
-    if (ctx->timing) {
-        if (ctx->log_used + 1 > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
-        ctx->call_first = ctx->log_used;
-        ctx->log_used += 1;
-        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
-            hipEvent_t e;
-            HIP_CHECK(make_event(&e, true));
-            ctx->events.push_back(e);
-        }
-        ctx->timed_calls = 1;
-    }
-    // a previous render of this context's on another stream may still run its sample kernel (the
-    // counters, flags, ring and sums are the sample kernel's own); the per-sample buffer this call
-    // writes may still be read by the reduce pass of an earlier call (on any stream)
-    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
+    hipEvent_t* ev = nullptr;
+    rc = open_call(ctx, s, 1, &ev);
+    if (rc) return rc;
+    // the per-sample buffer this call writes may still be read by the reduce pass of an earlier call
+    // (on any stream)
     if (direct && ctx->reduced_valid[sbuf]) HIP_CHECK(hipStreamWaitEvent(s, ctx->reduced[sbuf], 0));
     // the pending pass this launch folds in its tail (the flush above left only a foldable one)
     const bool folding = defer_fold && ctx->fold_pending;
@@ -1039,15 +861,13 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
     } else if (!direct) {
         HIP_CHECK(hipMemsetAsync(ctx->d_flags, 0, flag_bytes, s));
     }
-    hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
     if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
     trace_mark("launch_setup");
     HIP_CHECK(launch(&ua, nullptr));
     trace_mark("launch_issue");
     if (ev) HIP_CHECK(hipEventRecord(ev[1], s));
-    HIP_CHECK(hipEventRecord(ctx->launched, s));
-    ctx->launched_valid = true;
-    ctx->launched_stream = s;
+    rc = record_launched(ctx, s);
+    if (rc) return rc;
     // the stream on which the output is complete: split calls continue on os, after the sample kernel
     hipStream_t rs = s;
     if (split) {
@@ -1059,14 +879,14 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
         if (p.prof) {
             // the instrumented kernels do not fold: the pass runs whole after them
             HIP_CHECK(rtk_launch_fold_rest(&ctx->fold, rs));
-            HIP_CHECK(hipEventRecord(ctx->reduced[ctx->fold_buf], rs));
+            rc = record_reduced(ctx, ctx->fold_buf, rs);
         } else {
             // every wave of the launch claims fold chunks until none is left before it exits
             // (path_loop), so the pass is complete with the kernel: no follow-up pass, and the next
             // launch on this stream finds the buffer free without waiting on the output stream
-            HIP_CHECK(hipEventRecord(ctx->reduced[ctx->fold_buf], s));
+            rc = record_reduced(ctx, ctx->fold_buf, s);
         }
-        ctx->reduced_valid[ctx->fold_buf] = true;
+        if (rc) return rc;
         ctx->fold_pending = false;
     }
     if (defer_fold) {
@@ -1090,13 +910,11 @@ int render_rows(rt_context* ctx, const rt_camera* cam, uint32_t output_format, u
         } else {
             HIP_CHECK(rtk_launch_reduce(&ua, rs));
         }
-        HIP_CHECK(hipEventRecord(ctx->reduced[sbuf], rs));
-        ctx->reduced_valid[sbuf] = true;
+        rc = record_reduced(ctx, sbuf, rs);
+        if (rc) return rc;
     }
     if (ev) HIP_CHECK(hipEventRecord(ev[3], rs));
-    HIP_CHECK(hipEventRecord(ctx->done, rs));
-    ctx->done_valid = true;
-    return RT_OK;
+    return record_done(ctx, rs);
 }
 
 }  // namespace
@@ -1135,10 +953,7 @@ int rt_render_rows_accumulate(rt_context* ctx, const rt_camera* cam, uint32_t ro
     if (!cam) { rt_set_last_error("null camera"); return RT_ERR_INVALID; }
     if (!d_accum) { rt_set_last_error("null accumulator"); return RT_ERR_INVALID; }
     if (sample_count == 0 || n_rows == 0) return RT_OK;
-    if ((uint64_t)sample_begin + sample_count > 0xffffffffull) {
-        rt_set_last_error("sample_begin + sample_count exceeds 2^32 - 1");
-        return RT_ERR_INVALID;
-    }
+    if (const int rc = check_sample_range(sample_begin, sample_count)) return rc;
     // the pass is a plain one-stream launch of its own samples: the camera's sample count (unused by
     // the contract) becomes the pass's, which sizes the schedule, the unit mode and the BVH training;
     // nothing is scaled (rt_accum_resolve does that)
@@ -1176,19 +991,13 @@ int rt_render_rows_features(rt_context* ctx, const rt_camera* cam, uint32_t row0
     const bool empty = sample_count == 0 || n_rows == 0;
     if (row_step == 0) row_step = 1;
     if (!empty) {
-        if ((uint64_t)sample_begin + sample_count > 0xffffffffull) {
-            rt_set_last_error("sample_begin + sample_count exceeds 2^32 - 1");
-            return RT_ERR_INVALID;
-        }
+        int rc = check_sample_range(sample_begin, sample_count);
+        if (rc) return rc;
         rt_camera c = *cam;  // samples_per_pixel / pixel_samples_scale / bounce_max are unused by the contract
         c.samples_per_pixel = 1;
-        const int rc = validate_camera(&c);
+        rc = validate_camera(&c);
+        if (!rc) rc = check_rows(cam, row0, row_step, n_rows);
         if (rc) return rc;
-        const uint64_t last_row = (uint64_t)row0 + (uint64_t)(n_rows - 1) * row_step;
-        if (last_row >= cam->image_height) {
-            rt_set_last_error("row range exceeds image_height");
-            return RT_ERR_INVALID;
-        }
     }
     if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
     if (empty) return RT_OK;
@@ -1197,11 +1006,7 @@ int rt_render_rows_features(rt_context* ctx, const rt_camera* cam, uint32_t row0
     hipStream_t s = (hipStream_t)stream;
     HIP_CHECK(hipSetDevice(ctx->device));
     int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
-    if (!rc && !ctx->d_ctr) {
-        size_t cb = 0;
-        rc = ensure_buffer(ctx, (void**)&ctx->d_ctr, &cb, rtk::kCtrBytes);
-        if (!rc) HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrBytes, s));  // as render_rows: on the launch stream
-    }
+    if (!rc) rc = ensure_counters(ctx, s);
     if (rc) return rc;
     const bool bvh = use_bvh(ctx);
     const uint64_t P = (uint64_t)n_rows * cam->image_width;
@@ -1215,34 +1020,12 @@ int rt_render_rows_features(rt_context* ctx, const rt_camera* cam, uint32_t row0
     fa.hits = d_hits;
     fa.ctr = ctx->d_ctr;
     fa.P = (uint32_t)P;
-    if (ctx->timing) {
-        if (ctx->log_used + 1 > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
-        ctx->call_first = ctx->log_used;
-        ctx->log_used += 1;
-        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
-            hipEvent_t e;
-            HIP_CHECK(make_event(&e, true));
-            ctx->events.push_back(e);
-        }
-        ctx->timed_calls = 1;
-    }
-    // the tree and the scene are read-only here, but `launched` / `done` are re-recorded below: a
-    // previous render on another stream is waited for first, so the events still cover it
-    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
-    hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
+    hipEvent_t* ev = nullptr;
+    rc = open_call(ctx, s, 1, &ev);
+    if (rc) return rc;
     if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
     HIP_CHECK(rtk_launch_features(&p, bvh ? &ctx->bvh : nullptr, ctx->d_geo, ctx->d_mat, &fa, s, &ctx->last_kernel));
-    if (ev) {  // the pass is the sample kernel; there is no reduce pass (an empty interval)
-        HIP_CHECK(hipEventRecord(ev[1], s));
-        HIP_CHECK(hipEventRecord(ev[2], s));
-        HIP_CHECK(hipEventRecord(ev[3], s));
-    }
-    HIP_CHECK(hipEventRecord(ctx->launched, s));
-    ctx->launched_valid = true;
-    ctx->launched_stream = s;
-    HIP_CHECK(hipEventRecord(ctx->done, s));
-    ctx->done_valid = true;
-    return RT_OK;
+    return close_call(ctx, s, ev);
 }
 
 // ---- adaptive sampling (rt.h) ---------------------------------------------------
@@ -1293,20 +1076,8 @@ int rt_render_pixels_accumulate(rt_context* ctx, const rt_camera* cam, const uin
     const uint32_t n_per = (uint32_t)std::min<uint64_t>({(uint64_t)sample_count, cap / per_sample, 0xffffffffull / L});
     hipStream_t s = (hipStream_t)stream;
     HIP_CHECK(hipSetDevice(ctx->device));
-    if (needs_far_rebuild(ctx->scene, c)) {
-        rc = quiesce(ctx);  // the previous render may still walk the old tree
-        if (rc) return rc;
-        build_bvh(ctx->scene, far_bound(ctx->scene, c));
-        rc = upload_bvh(ctx);
-        if (rc) return rc;
-    }
-    if (needs_training(ctx->scene, c, L * sample_count)) {
-        rc = quiesce(ctx);
-        if (rc) return rc;
-        train_bvh(ctx->scene, c);
-        rc = upload_bvh(ctx);
-        if (rc) return rc;
-    }
+    rc = prepare_tree(ctx, c, L * sample_count);
+    if (rc) return rc;
     rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
     // the workspace of direct mode, one sample buffer (rt.h "Workspace").  A larger buffer is kept as it
     // is: an adaptive loop's lists shrink from round to round, and giving memory back every time the
@@ -1318,28 +1089,14 @@ int rt_render_pixels_accumulate(rt_context* ctx, const rt_camera* cam, const uin
     if (!rc) rc = ensure_buffer(ctx, (void**)&ctx->d_samples, &ctx->samples_bytes, (size_t)(per_sample * n_per));
     if (!rc) rc = release_buffer(ctx, (void**)&ctx->d_samples2, &ctx->samples2_bytes);
     ctx->samples_flip = 0;
-    if (!rc && !ctx->d_ctr) {
-        size_t cb = 0;
-        rc = ensure_buffer(ctx, (void**)&ctx->d_ctr, &cb, rtk::kCtrBytes);
-        if (!rc) HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrBytes, s));  // as render_rows: on the launch stream
-    }
+    if (!rc) rc = ensure_counters(ctx, s);
     if (rc) return rc;
     const bool bvh = use_bvh(ctx);
     const uint32_t n_sub = (sample_count + n_per - 1) / n_per;
     // timing: one slot of the event log per sub-pass (at most kMaxTimed of them are timed)
-    const uint32_t n_timed = ctx->timing ? std::min(n_sub, kMaxTimed) : 0u;
-    if (n_timed) {
-        if (ctx->log_used + n_timed > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
-        ctx->call_first = ctx->log_used;
-        ctx->log_used += n_timed;
-        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
-            hipEvent_t e;
-            HIP_CHECK(make_event(&e, true));
-            ctx->events.push_back(e);
-        }
-        ctx->timed_calls = n_timed;
-    }
-    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
+    hipEvent_t* ev0 = nullptr;
+    rc = open_call(ctx, s, n_sub, &ev0);
+    if (rc) return rc;
     if (ctx->reduced_valid[0]) HIP_CHECK(hipStreamWaitEvent(s, ctx->reduced[0], 0));
     rtk::KernelParams p = make_params(&c, 0, 1, c.image_height, ctx->n_spheres);
     const rtk::GatherArgs ga{d_pixels, d_counts};
@@ -1361,7 +1118,7 @@ int rt_render_pixels_accumulate(rt_context* ctx, const rt_camera* cam, const uin
         ua.stall_ticks = stall_bound(bvh, ctx->n_spheres);
         ua.scale = 1.0;
         HIP_CHECK(hipMemsetAsync(ctx->d_ctr, 0, rtk::kCtrLaunchBytes, s));  // not the sticky error word
-        hipEvent_t* ev = k < n_timed ? &ctx->events[kEventsPerCall * (ctx->call_first + k)] : nullptr;
+        hipEvent_t* ev = ev0 && k < ctx->timed_calls ? ev0 + kEventsPerCall * k : nullptr;
         if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
         HIP_CHECK(rtk_launch_gather(&p, bvh ? &ctx->bvh : nullptr, bvh && ctx->precision == RT_PRECISION_F32, ctx->d_geo,
                                     ctx->d_mat, &ua, &ga, d_stats, s, &ctx->last_kernel));
@@ -1371,14 +1128,7 @@ int rt_render_pixels_accumulate(rt_context* ctx, const rt_camera* cam, const uin
         HIP_CHECK(rtk_launch_gather_reduce(&ra, s));
         if (ev) HIP_CHECK(hipEventRecord(ev[3], s));
     }
-    HIP_CHECK(hipEventRecord(ctx->launched, s));
-    ctx->launched_valid = true;
-    ctx->launched_stream = s;
-    HIP_CHECK(hipEventRecord(ctx->reduced[0], s));
-    ctx->reduced_valid[0] = true;
-    HIP_CHECK(hipEventRecord(ctx->done, s));
-    ctx->done_valid = true;
-    return RT_OK;
+    return close_call(ctx, s, nullptr, 0);  // the sub-passes recorded their slots; the last read buffer 0
 }
 
 int rt_accum_select(rt_context* ctx, const void* d_accum, const void* d_m2, const uint32_t* d_counts, uint64_t n_pixels,
@@ -1497,20 +1247,9 @@ int rt_denoise(rt_context* ctx, uint32_t width, uint32_t height, const void* d_a
     if (const char* e = std::getenv("RTZIG_DENOISE_FORM")) force = std::strcmp(e, "tile") == 0 ? 1 : std::strcmp(e, "direct") == 0 ? 2 : 0;
     double* g = (double*)ctx->d_denoise;  // [P][8], then the two [P][4] planes
     double* cv[2] = {g + 8 * (size_t)P, g + 12 * (size_t)P};
-    if (ctx->timing) {
-        if (ctx->log_used + 1 > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
-        ctx->call_first = ctx->log_used;
-        ctx->log_used += 1;
-        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
-            hipEvent_t e;
-            HIP_CHECK(make_event(&e, true));
-            ctx->events.push_back(e);
-        }
-        ctx->timed_calls = 1;
-    }
-    // the planes belong to the context: a previous call on another stream is waited for first
-    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
-    hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
+    hipEvent_t* ev = nullptr;
+    rc = open_call(ctx, s, 1, &ev);
+    if (rc) return rc;
     if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
     rtk::DenoisePrepareArgs pa{};
     pa.accum = (const double*)d_accum;
@@ -1541,18 +1280,9 @@ int rt_denoise(rt_context* ctx, uint32_t width, uint32_t height, const void* d_a
                           rtk_denoise_tile_ok(width, height, la.step);
         HIP_CHECK(rtk_launch_denoise_level(&la, tile ? 1 : 0, s));
     }
-    if (ev) {  // the call is reported as the sample kernel; there is no reduce pass (an empty interval)
-        HIP_CHECK(hipEventRecord(ev[1], s));
-        HIP_CHECK(hipEventRecord(ev[2], s));
-        HIP_CHECK(hipEventRecord(ev[3], s));
-    }
-    HIP_CHECK(hipEventRecord(ctx->launched, s));
-    ctx->launched_valid = true;
-    ctx->launched_stream = s;
-    HIP_CHECK(hipEventRecord(ctx->done, s));
-    ctx->done_valid = true;
-    ctx->last_kernel = "denoise";
-    return RT_OK;
+    rc = close_call(ctx, s, ev);
+    if (!rc) ctx->last_kernel = "denoise";
+    return rc;
 }
 
 // ---- temporal accumulation (rt.h) -------------------------------------------------
@@ -1639,7 +1369,7 @@ int rt_temporal_accumulate(rt_context* ctx, const rt_camera* cam, const rt_tempo
     if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
     hipStream_t s = (hipStream_t)stream;
     HIP_CHECK(hipSetDevice(ctx->device));
-    const int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
     if (rc) return rc;
     const rt_temporal_frame* src[2] = {cur, prev};
     rtk::TemporalFrame* dst[2] = {&ta.cur, &ta.prev};
@@ -1659,35 +1389,14 @@ int rt_temporal_accumulate(rt_context* ctx, const rt_camera* cam, const rt_tempo
     ta.W = cam->image_width;
     ta.H = cam->image_height;
     ta.history = d_history;
-    if (ctx->timing) {
-        if (ctx->log_used + 1 > kMaxTimed) ctx->log_used = 0;  // wrap: totals restart
-        ctx->call_first = ctx->log_used;
-        ctx->log_used += 1;
-        while (ctx->events.size() < kEventsPerCall * (size_t)ctx->log_used) {
-            hipEvent_t e;
-            HIP_CHECK(make_event(&e, true));
-            ctx->events.push_back(e);
-        }
-        ctx->timed_calls = 1;
-    }
-    // nothing of the context is read, but `launched` / `done` are re-recorded below: a previous call on
-    // another stream is waited for first, so the events still cover it
-    if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
-    hipEvent_t* ev = ctx->timing ? &ctx->events[kEventsPerCall * ctx->call_first] : nullptr;
+    hipEvent_t* ev = nullptr;
+    rc = open_call(ctx, s, 1, &ev);
+    if (rc) return rc;
     if (ev) HIP_CHECK(hipEventRecord(ev[0], s));
     HIP_CHECK(rtk_launch_temporal(&ta, s));
-    if (ev) {  // the call is reported as the sample kernel; there is no reduce pass (an empty interval)
-        HIP_CHECK(hipEventRecord(ev[1], s));
-        HIP_CHECK(hipEventRecord(ev[2], s));
-        HIP_CHECK(hipEventRecord(ev[3], s));
-    }
-    HIP_CHECK(hipEventRecord(ctx->launched, s));
-    ctx->launched_valid = true;
-    ctx->launched_stream = s;
-    HIP_CHECK(hipEventRecord(ctx->done, s));
-    ctx->done_valid = true;
-    ctx->last_kernel = "temporal_accumulate";
-    return RT_OK;
+    rc = close_call(ctx, s, ev);
+    if (!rc) ctx->last_kernel = "temporal_accumulate";
+    return rc;
 }
 
 int rt_context_fold_pending(rt_context* ctx, int* pending) {

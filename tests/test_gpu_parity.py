@@ -487,6 +487,87 @@ def test_kernel_times_total_accumulates():
     r.close()
 
 
+def test_event_log_across_call_kinds(monkeypatch):
+    """Every call kind reserves its slots of the one event log through the same code: a row render, a
+    feature pass, a gather pass in 2 sub-passes, a denoise and a temporal accumulation on one timed
+    context log 1 + 1 + 2 + 1 + 1 launches, kernel_times() after each call covers that call's own
+    slots (it equals what the call added to the totals), and the passes in between disturb nothing:
+    the same render afterwards has the bits of a fresh context's."""
+    import torch
+    dev = "cuda:0"
+    monkeypatch.setenv("RTZIG_UNIT_MODE", "direct")
+    scene = rtzig.Scene.init(5)
+    scene.world = (RtSphere * 3)(
+        RtSphere(center=D3(0, -100.5, -1), radius=100.0, material=RT_LAMBERTIAN, albedo=D3(0.8, 0.8, 0.0)),
+        RtSphere(center=D3(0, 0, -1.2), radius=0.5, material=RT_LAMBERTIAN, albedo=D3(0.1, 0.2, 0.5)),
+        RtSphere(center=D3(1, 0, -1), radius=0.5, material=RT_METAL, albedo=D3(0.8, 0.6, 0.2), fuzz=0.3))
+    cam = rtzig.Camera.builder(16, 2.0).setScene(scene).setSamplesPerPixel(4).build()
+    W, H, P = cam.width, cam.height, cam.width * cam.height
+    assert (W, H) == (16, 8)
+
+    def f64(*shape):
+        return torch.zeros(shape, dtype=torch.float64, device=dev)
+
+    def frame():  # the buffers of one image: gather sums, feature sums
+        return dict(accum=f64(P, 3), m2=f64(P), counts=torch.zeros(P, dtype=torch.int32, device=dev),
+                    albedo=f64(P, 3), normal=f64(P, 3), depth=f64(P), hits=torch.zeros(P, dtype=torch.int32, device=dev))
+
+    cur, prev = frame(), frame()
+    r = rtzig.DeviceRenderer(0)
+    r.set_scene(scene.world)
+    fill = rtzig.DeviceRenderer(0)  # the previous frame's buffers, from an untimed context
+    fill.set_scene(scene.world)
+    fill.features(cam.cam, 0, 2, prev["albedo"].data_ptr(), prev["normal"].data_ptr(), prev["depth"].data_ptr(),
+                  prev["hits"].data_ptr())
+    fill.accumulate_pixels(cam.cam, None, 4, prev["accum"].data_ptr(), prev["m2"].data_ptr(), prev["counts"].data_ptr())
+    fill.sync()
+    fill.close()
+
+    out, den = f64(H, W, 3), f64(H, W, 3)
+    ptrs = lambda fr: dict({k: v.data_ptr() for k, v in fr.items()}, feature_samples=2)  # noqa: E731
+    calls = [
+        (1, lambda: r.render_rows_async(cam.cam, out.data_ptr())),
+        (1, lambda: r.features(cam.cam, 0, 2, cur["albedo"].data_ptr(), cur["normal"].data_ptr(),
+                               cur["depth"].data_ptr(), cur["hits"].data_ptr())),
+        # a cap of 2 samples of the 128 pixels (and a little): 4 samples run as 2 + 2
+        (2, lambda: r.accumulate_pixels(cam.cam, None, 4, cur["accum"].data_ptr(), cur["m2"].data_ptr(),
+                                        cur["counts"].data_ptr())),
+        (1, lambda: r.denoise(W, H, cur["accum"].data_ptr(), cur["m2"].data_ptr(), cur["counts"].data_ptr(),
+                              den.data_ptr(), cur["albedo"].data_ptr(), cur["normal"].data_ptr(),
+                              cur["depth"].data_ptr(), cur["hits"].data_ptr(), feature_samples=2)),
+        (1, lambda: r.temporal_accumulate(cam.cam, ptrs(cur), cam.cam, ptrs(prev))),
+    ]
+    monkeypatch.setenv("RTZIG_GATHER_BYTES", str(P * 24 * 2 + 100))
+    r.enable_timing(True)
+    total = (0.0, 0.0, 0)
+    for slots, call in calls:
+        call()
+        own = r.kernel_times()
+        after = r.kernel_times_total()
+        print("slots", after[2] - total[2], "own", own, "total", after)
+        assert after[2] - total[2] == slots
+        assert all(math.isfinite(t) and t >= 0 for t in own + after[:2])
+        # HIP event times are f32 milliseconds: the sums agree far inside 1e-3 ms
+        assert abs(after[0] - total[0] - own[0]) < 1e-3 and abs(after[1] - total[1] - own[1]) < 1e-3
+        total = after
+    assert total[2] == 6
+    r.sync()
+    first = out.cpu().numpy().copy()
+    assert int(cur["counts"].min()) >= 4  # the gather pass ran (the temporal pass may add pseudo-samples)
+    out.fill_(-1.0)
+    r.render_rows_async(cam.cam, out.data_ptr())  # after the interleaved passes, on the same context
+    r.sync()
+    again = out.cpu().numpy().copy()
+    r.close()
+    fresh = rtzig.DeviceRenderer(0)
+    fresh.set_scene(scene.world)
+    ref = f64(H, W, 3)
+    fresh.render_rows_async(cam.cam, ref.data_ptr())
+    fresh.sync()
+    fresh.close()
+    assert np.array_equal(first, ref.cpu().numpy()) and np.array_equal(again, ref.cpu().numpy())
+
+
 @pytest.mark.parametrize("mode", ["ring", "direct"])
 @pytest.mark.parametrize("spp", [1, 2, 3, 15, 16, 17, 31, 33, 47, 48, 49, 95, 97, 100])
 def test_unit_schedule_sample_counts_bit_exact(oracle, spp, mode, monkeypatch):

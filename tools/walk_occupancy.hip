@@ -221,7 +221,7 @@ __global__ __launch_bounds__(B) __attribute__((amdgpu_waves_per_eu(kWaves, kWave
 
 namespace {
 
-// device tree of rt_runtime.cpp's set_tree (tools keep their own copy of the conversion)
+// device tree of rt_scene.cpp's set_tree (tools keep their own copy of the conversion)
 struct DevTree {
     std::vector<rtk::BvhNode> nodes;
     std::vector<rtk::BvhLeaf> leaves;
@@ -329,7 +329,7 @@ int main(int argc, char** argv) {
     p.v_up[1] = 1; p.vfov = 20; p.defocus_angle = 0.6; p.focus_dist = 10; p.t_min = 1e-3; p.t_max = INFINITY;
     rt_camera cam;
     rt_camera_build(&p, &cam);
-    // the runtime's tree for config 4: SAH, then trained on 6000 camera samples (rt_runtime.cpp)
+    // the runtime's tree for config 4: SAH, then trained on 6000 camera samples (rt_scene.cpp)
     const double bound = rtbvh::scene_extent(sp.data(), n) * (1.0 + 0x1p-20) + 1e-300;
     const rtbvh::Bvh sah = rtbvh::build(sp.data(), n, bound);
     const auto train = rtbvh::sample_rays(sp.data(), n, cam, sah, 6000, 0x7261792d74726565ull);
