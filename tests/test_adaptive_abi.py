@@ -6,7 +6,7 @@ does for the kernels they are twins of), and render_adaptive validates its argum
 import ctypes as C
 import os
 import re
-import subprocess
+import sys
 
 import pytest
 
@@ -16,6 +16,8 @@ from rtzig.lib import EXPORTED
 
 RT_ERR_INVALID = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_build  # noqa: E402
 NAN = float("nan")
 
 
@@ -123,22 +125,7 @@ def test_render_adaptive_rejects_bad_arguments_before_any_device_work(kw):
 
 # ---- the gather kernels' register budget (build time) ----------------------------------------------
 def _resources():
-    err = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
-                          "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "rt_kernel.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"],
-                         cwd=os.path.join(ROOT, "raytracing-with-zig_amd", "csrc"), capture_output=True, text=True,
-                         check=True).stderr
-    cur, rows = None, {}
-    for line in err.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rows[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur:
-            rows[cur][m.group(1)] = int(m.group(2))
-    return rows
+    return kernel_build.resources("rt_kernel.hip")
 
 
 def test_six_gather_kernels_no_scratch_lds_tree_ones_at_four_waves():

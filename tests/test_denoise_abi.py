@@ -8,7 +8,7 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -20,6 +20,8 @@ from rtzig.lib import EXPORTED
 
 RT_ERR_INVALID = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_build  # noqa: E402
 DEFAULTS = dict(levels=2, reserved=0, sigma_l=4.0, sigma_n=32.0, sigma_a=32.0, sigma_z=0.05, sigma_h=4.0,
                 epsilon=1e-6)
 
@@ -151,23 +153,7 @@ def test_render_denoised_rejects_bad_arguments_before_any_device_work(kw):
 
 # ---- the denoise kernels' resources (build time) ----------------------------------------------------
 def _resources():
-    err = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
-                          "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "rt_denoise.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"],
-                         cwd=os.path.join(ROOT, "raytracing-with-zig_amd", "csrc"), capture_output=True, text=True,
-                         check=True).stderr
-    cur, rows = None, {}
-    for line in err.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rows[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)",
-                      line)
-        if m and cur:
-            rows[cur][m.group(1)] = int(m.group(2))
-    return rows
+    return kernel_build.resources("rt_denoise.hip")
 
 
 def test_denoise_kernels_exist_without_scratch_outside_the_other_counts():

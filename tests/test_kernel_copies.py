@@ -18,10 +18,11 @@ handout        0 + 12                           0 + 8
 """
 import collections
 import os
-import subprocess
-import tempfile
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_build  # noqa: E402
 KERNEL = "_ZN3rtk17sample_kernel_bvhILb1ELb0ELb0E"
 
 # region: (budget, the parent's count)
@@ -38,13 +39,7 @@ BUDGET = {
 
 
 def _copies():
-    with tempfile.TemporaryDirectory(prefix="rtzig_copies_") as d:
-        out = os.path.join(d, "k.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
-                        "--offload-arch=gfx950", "-fno-gpu-rdc", "-DRTZIG_MARKS=1", "--cuda-device-only", "-S",
-                        "rt_kernel.hip", "-o", out],
-                       cwd=os.path.join(ROOT, "raytracing-with-zig_amd", "csrc"), capture_output=True, text=True, check=True)
-        lines = open(out).read().split("\n")
+    lines = kernel_build.assembly("rt_kernel.hip", ("-DRTZIG_MARKS=1",))
     start = next(i for i, l in enumerate(lines) if l.startswith(KERNEL))
     counts, region = collections.Counter(), "prologue"
     for l in lines[start + 1:]:

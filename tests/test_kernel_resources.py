@@ -5,28 +5,15 @@ profiles/r04_occupancy), and the uninstrumented BVH kernels keep 4 waves per SIM
 DESIGN §5.1)."""
 import os
 import re
-import subprocess
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_build  # noqa: E402
 
 
 def _resources():
-    err = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
-                          "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "rt_kernel.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"],
-                         cwd=os.path.join(ROOT, "raytracing-with-zig_amd", "csrc"), capture_output=True, text=True,
-                         check=True).stderr
-    cur, rows = None, {}
-    for line in err.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rows[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]): (\d+)", line)
-        if m and cur:
-            rows[cur][m.group(1)] = int(m.group(2))
-    return rows
+    return kernel_build.resources("rt_kernel.hip")
 
 
 def test_no_scratch_and_bvh_kernels_at_four_waves():

@@ -8,7 +8,7 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -20,6 +20,8 @@ from rtzig.lib import EXPORTED
 
 RT_ERR_INVALID = -1
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_build  # noqa: E402
 DEFAULTS = dict(max_history=64, reserved=0, sigma_z=0.05, tau_n=0.1, tau_a=0.05, tau_h=0.5, min_weight=0.25)
 
 
@@ -203,23 +205,7 @@ def test_render_sequence_rejects_bad_arguments_before_any_device_work(kw):
 
 # ---- the kernel's resources (build time) ---------------------------------------------------------------
 def _resources():
-    err = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-x", "hip",
-                          "--offload-arch=gfx950", "-fno-gpu-rdc", "-c", "rt_temporal.hip", "-o", os.devnull,
-                          "-Rpass-analysis=kernel-resource-usage"],
-                         cwd=os.path.join(ROOT, "raytracing-with-zig_amd", "csrc"), capture_output=True, text=True,
-                         check=True).stderr
-    cur, rows = None, {}
-    for line in err.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = m.group(1)
-            rows[cur] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)",
-                      line)
-        if m and cur:
-            rows[cur][m.group(1)] = int(m.group(2))
-    return rows
+    return kernel_build.resources("rt_temporal.hip")
 
 
 def test_one_temporal_kernel_without_scratch_or_lds():

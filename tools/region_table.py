@@ -35,11 +35,8 @@ import collections
 import json
 import os
 import re
-import subprocess
-import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "raytracing-with-zig_amd", "csrc", "rt_kernel.hip")
 KERNEL = "_ZN3rtk17sample_kernel_bvhILb1ELb0ELb0E"
 F64 = re.compile(r"^v_(add|mul|fma|fmac)_f64|^v_(rsq|rcp|sqrt)_f64|^v_div_(scale|fmas|fixup)_f64|^v_cmp\w*_f64|^v_(min|max)_f64|^v_cvt_f64")
 
@@ -48,6 +45,7 @@ RATES = os.path.join(ROOT, "profiles", "r05_peak", "issue_rates.json")
 import sys  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import issue_rates  # noqa: E402
+import kernel_build  # noqa: E402
 
 
 def load_rates(path=RATES):
@@ -84,10 +82,7 @@ def rate(op, rates):
 
 
 def asm(extra):
-    out = os.path.join(tempfile.mkdtemp(prefix="rtzig_regions_"), "k.s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-ffp-contract=off", "-x", "hip", "--offload-arch=gfx950",
-                    "--cuda-device-only", "-S", SRC, "-o", out, *extra], check=True, capture_output=True)
-    return open(out).read().split("\n")
+    return list(kernel_build.assembly("rt_kernel.hip", tuple(extra)))
 
 
 def blocks_of(lines, kernel):
