@@ -473,6 +473,57 @@ int rt_temporal_accumulate(rt_context* ctx,
                            const rt_camera* cam, const rt_temporal_frame* cur,
                            const rt_camera* cam_prev, const rt_temporal_frame* prev,
                            const rt_temporal_params* params, uint32_t* d_history, void* stream);
+/* ---- ray queries: the closest hit of caller-supplied rays, bit-exact --------------
+ * HittableList.hit(ray, Interval(t_min, t_max)) (hittable.zig:64-77 over Sphere.hit, sphere.zig:26-54)
+ * for n_rays rays in DEVICE memory, in the reference's f64 arithmetic, bit for bit.
+ * d_origins, d_directions: f64, ray q at [q * ray_stride + 0..2]; ray_stride is in doubles, 0 means 3,
+ * 4 is Zig's @Vector(3, f64); 1 and 2 are invalid.  Directions are used as given, not normalised.
+ * d_intervals: NULL, or [n][2] f64 — ray q then uses (intervals[q][0], intervals[q][1]) in place of
+ * (t_min, t_max).
+ *
+ * Per ray: the sphere with the smallest accepted root wins, the lowest index among equal roots;
+ * Interval.surrounds is strict at both ends; a sphere's root is root1, else root2 (sphere.zig:38-42).
+ * The record follows sphere.zig:44-53: point = orig + dir * t; outward = (point - center) * inv_r;
+ * front = dot(dir, outward) < 0; normal = front ? outward : -outward.  Every non-NULL output is written
+ * for every ray, so the buffers need not be initialised.  NaN and infinite components and intervals
+ * are legal: the result is what the reference's comparisons give (a miss wherever a NaN decides), and
+ * the call neither faults nor hangs.  Inputs and outputs must not alias.
+ *
+ * The arithmetic is always parity, whatever rt_context_set_precision says.  Instrumented contexts are
+ * accepted.  The call walks the structure the context holds now (rt_context_tree_info) and never
+ * rebuilds or trains it.  The tree's f32 boxes are used only for rays inside the domain they are
+ * certified for (finite components, max|o_k| <= rt_context_origin_bound, max|d_k| in [2^-20, 2^20],
+ * 0 <= t_min < +inf; csrc/rt_trace.h); every other ray is answered by the reference's own scan of the
+ * whole list: the same bits, at the list's cost.
+ *
+ * d_stats (DEVICE, 2 x uint64, may be NULL) is atomically incremented: [0] by the number of rays, [1]
+ * by the number of rays the list scan resolved (every ray when the context walks the list).
+ *
+ * Launch: asynchronous on `stream`, one kernel, a plain one-stream call (a pending deferred reduce pass
+ * runs first).  No workspace.  rt_context_kernel_times reports it as sample_ms, with reduce_ms 0.
+ * n_rays == 0: RT_OK, nothing is touched.  All five outputs NULL and d_stats NULL: RT_OK, no launch.
+ * RT_ERR_INVALID, each answered before any device is touched: null d_origins, d_directions or out;
+ * ray_stride 1 or 2; n_rays >= 2^32; null ctx; no scene uploaded. */
+typedef struct rt_ray_hits {   /* DEVICE pointers; each may be NULL: that output is skipped */
+    int32_t* index;            /* [n]    sphere index in rt_context_set_scene's list; -1: miss */
+    double*  t;                /* [n]    the accepted root; +inf on a miss */
+    double*  point;            /* [n][3] ray.at(t);            +0.0 on a miss */
+    double*  normal;           /* [n][3] after setFaceNormal;  +0.0 on a miss */
+    uint8_t* front;            /* [n]    1 iff dot(dir, outward) < 0; 0 on a miss */
+} rt_ray_hits;                 /* 40 bytes */
+int rt_trace_rays(rt_context* ctx, const void* d_origins, const void* d_directions,
+                  uint32_t ray_stride, uint64_t n_rays, double t_min, double t_max,
+                  const void* d_intervals, const rt_ray_hits* out, void* d_stats, void* stream);
+/* The origin bound of the tree the context holds: rays starting within it (max|o_k| <= bound) may use
+ * the tree; rays starting beyond it are exact but cost a scan of the whole list.  0 when the list walk
+ * runs. */
+int rt_context_origin_bound(rt_context* ctx, double* bound);
+/* The remedy for that cost: with a finite bound greater than the current one, waits for the context's
+ * work and rebuilds the tree for origins up to bound * 1.01 (host work; the path a far camera takes).
+ * A smaller or equal bound, or a context without a tree, is a no-op.  It changes no result bit of any
+ * call.  It drops a trained tree: the next large render retrains.  RT_ERR_INVALID: a non-finite or
+ * non-positive bound; null ctx; no scene uploaded. */
+int rt_context_reserve_origin_bound(rt_context* ctx, double bound);
 /* Runs a pending deferred reduce pass (on the out_stream of the call that deferred it); no-op otherwise. */
 int rt_context_flush(rt_context* ctx);
 /* *pending = 1 if the last deferred call left its output pending (direct mode), else 0. */

@@ -6,6 +6,7 @@
 
 #include "rt_device.h"
 #include "rt_fastdiv.h"
+#include "rt_trace.h"
 
 namespace rtk {
 
@@ -161,6 +162,29 @@ struct FeatureArgs {
     // samples one after the other; 2 or 4: small launches — the kernel instantiation launched is the
     // one compiled for it), and the tiles of 64 >> spread pixels, a wave each
     uint32_t spread, n_tiles;
+};
+// Ray queries (rt_trace_rays): the closest hit of n_rays caller-supplied rays.  Ray q
+// is origins / directions[q * ray_stride + 0..2] (f64) with the interval intervals[q][0..1], or
+// (t_min, t_max) when `intervals` is nullptr.  Each output may be nullptr (not written).  The trace
+// kernels (trace_kernel*, rt_kernel.hip) take this as a LAST kernel argument, after the KernelParams
+// (of which they read n_spheres and n_pad only) and the BvhArgs, so the kernarg offsets the walker
+// reads stay put.
+struct TraceArgs {
+    const double* origins;
+    const double* directions;
+    const double* intervals;   // [n][2] or nullptr
+    int32_t* index;            // [n] sphere index, -1: miss
+    double* t;                 // [n] the accepted root, +inf: miss
+    double* point;             // [n][3]
+    double* normal;            // [n][3]
+    uint8_t* front;            // [n]
+    unsigned long long* stats; // {rays, rays resolved by the list scan} or nullptr
+    unsigned long long* ctr;   // kCtrBytes: [kErrWord] error word (RTZIG_BOUNDS debug builds)
+    double t_min, t_max;
+    uint32_t n_rays;           // > 0
+    uint32_t ray_stride;       // doubles between rays, >= 3
+    uint32_t n_tiles;          // set by rtk_launch_trace: tiles of 64 rays, a wave each
+    uint32_t pad;
 };
 // rt_accum_select: an ordered stream compaction in three launches, none of which
 // waits on another block.  Blocks of kSelBlock threads, one pixel each.  Scratch (the context's):
@@ -399,6 +423,12 @@ extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, h
 extern "C" hipError_t rtk_launch_features(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
                                           const rtk::MatRec* mat, const rtk::FeatureArgs* fa, hipStream_t stream,
                                           const char** name);
+// Ray queries (rtk::TraceArgs): the trace kernel of the structure the context holds — `b` == nullptr:
+// the list walk; else the BVH walk, in LDS by the feature launcher's rule — over ta->n_rays rays, a
+// wave per 64.  One launch, no workspace.  Only p->n_spheres and p->n_pad are read.
+extern "C" hipError_t rtk_launch_trace(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                       const rtk::MatRec* mat, const rtk::TraceArgs* ta, hipStream_t stream,
+                                       const char** name);
 // rt_accum_select's three launches (count, scan, scatter) over a->n pixels.
 extern "C" hipError_t rtk_launch_select(const rtk::SelectArgs* a, hipStream_t stream);
 // out[q] = accum[q] * (1.0 / counts[q]) (0 where counts[q] == 0), formats as rtk_launch_resolve.

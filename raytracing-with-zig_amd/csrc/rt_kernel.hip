@@ -43,6 +43,11 @@
 //   normal, depth and the hit count.  They reuse
 //   the camera functions and the walkers as they are; the existing kernels compile to the same
 //   instructions as before.
+//
+// Ray queries (rt_trace_rays, rt_kernel.h TraceArgs): trace_kernel (list walk) and trace_kernel_bvh
+//   run trace_loop — one lane per caller-supplied ray, its own interval, the whole hit record.  A ray
+//   outside the domain the tree's f32 boxes are certified for (rt_trace.h) takes the list scan.  The
+//   walkers are used as they are; the existing kernels compile to the same instructions as before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -2322,6 +2327,140 @@ __global__ __launch_bounds__(kBlockBvh) void feature_kernel_bvh(KernelParams p, 
                  }, geo_g, mat_g, fa);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Ray queries (rt_trace_rays, rt_kernel.h TraceArgs): HittableList.hit of rays the
+// caller supplies, each with its own interval.  A kernel family of its own: one lane per ray, a wave
+// per tile of 64 consecutive rays, tiles strided over the grid's waves as in feature_loop.
+// The walkers are used as they are.  The BVH walk's f32 slab tests are certified for the renderer's
+// rays only, so every lane first evaluates trace_tree_ok (rt_trace.h) on its ray in f64.  A lane that
+// passes walks the tree.  A lane that fails hands the walker a dummy instead — a NaN origin (every
+// sphere test fails on `disc >= 0`, every slab plane is a NaN that v_max3 / v_min3 drop), direction
+// (1, 0, 0) and the inverted interval (1, -1), which culls both children of the root — so it leaves
+// the walk after one node visit without a candidate block, and then takes the reference's own scan,
+// world_hit over the whole list, behind a wave-uniform ballot.  The list-walk kernels scan every ray.
+// ------------------------------------------------------------------------------------------------
+template <bool kTree, class Walker>
+__device__ __forceinline__ void trace_loop(const KernelParams& p, const Walker& walk,
+                                           const GeoRec* __restrict__ geo_orig, const MatRec* __restrict__ mat_g,
+                                           const TraceArgs& ta, double origin_bound) {
+    const uint32_t lane = lane_id();
+    const uint32_t waves = gridDim.x * (blockDim.x / 64);
+    const size_t stride = ta.ray_stride;
+    Prof<0> pr;
+    uint32_t n_rays = 0, n_scan = 0;  // this wave's counts (wave-uniform)
+    for (uint32_t tile = (threadIdx.x / 64) * gridDim.x + blockIdx.x; tile < ta.n_tiles; tile += waves) {
+        // the last tile's lanes past the last ray trace that ray again and store nothing
+        const uint32_t q0 = tile * 64 + lane;
+        const bool live = q0 < ta.n_rays;
+        const size_t q = live ? q0 : ta.n_rays - 1;
+        Ray r;
+        r.orig = mk(ta.origins[q * stride], ta.origins[q * stride + 1], ta.origins[q * stride + 2]);
+        r.dir = mk(ta.directions[q * stride], ta.directions[q * stride + 1], ta.directions[q * stride + 2]);
+        double t_min = ta.t_min, t_max = ta.t_max;
+        if (ta.intervals) {
+            t_min = ta.intervals[2 * q];
+            t_max = ta.intervals[2 * q + 1];
+        }
+        double t;
+        int k;
+        bool scan = true;
+        if constexpr (kTree) {
+            const double o3[3] = {r.orig.x, r.orig.y, r.orig.z}, d3[3] = {r.dir.x, r.dir.y, r.dir.z};
+            const bool ok = trace_tree_ok(o3, d3, t_min, t_max, origin_bound);
+            scan = !ok;
+            const double nan = __builtin_nan("");
+            Ray rw;
+            rw.orig = mk(ok ? r.orig.x : nan, ok ? r.orig.y : nan, ok ? r.orig.z : nan);
+            rw.dir = mk(ok ? r.dir.x : 1.0, ok ? r.dir.y : 0.0, ok ? r.dir.z : 0.0);
+            k = walk(rw, ok ? t_min : 1.0, ok ? t_max : -1.0, &t, pr);
+            if (__ballot(scan) != 0) {
+                if (scan) k = world_hit<1>(geo_orig, p.n_pad, r, t_min, t_max, &t);
+            }
+        } else {
+            k = walk(r, t_min, t_max, &t, pr);
+        }
+        const bool hit = k >= 0 && bounds_ok((uint32_t)k < p.n_spheres, ta.ctr);
+        v3 pt = mk(0, 0, 0), nrm = mk(0, 0, 0);
+        bool front = false;
+        if (hit) {
+            // hit record (sphere.zig:44-53), the operations of path_loop's shading block
+            const GeoRec sg = geo_orig[k];
+            const MatRec m = mat_g[k];
+            pt = r.orig + muls(r.dir, t);
+            const v3 outward = muls(pt - mk(sg.cx, sg.cy, sg.cz), m.inv_r);
+            front = dot(r.dir, outward) < 0;
+            nrm = front ? outward : -outward;
+        }
+        if (live) {
+            if (ta.index) ta.index[q] = hit ? k : -1;
+            if (ta.t) ta.t[q] = hit ? t : __builtin_inf();
+            if (ta.point) {
+                ta.point[3 * q] = pt.x;
+                ta.point[3 * q + 1] = pt.y;
+                ta.point[3 * q + 2] = pt.z;
+            }
+            if (ta.normal) {
+                ta.normal[3 * q] = nrm.x;
+                ta.normal[3 * q + 1] = nrm.y;
+                ta.normal[3 * q + 2] = nrm.z;
+            }
+            if (ta.front) ta.front[q] = front ? 1 : 0;
+        }
+        n_rays += (uint32_t)__popcll(__ballot(live));
+        n_scan += (uint32_t)__popcll(__ballot(live && scan));
+    }
+    // {rays, rays resolved by the list scan}: one vector atomic per wave and word
+    if (ta.stats && lane == 0 && n_rays) {
+        atomicAdd(ta.stats, (unsigned long long)n_rays);
+        if (n_scan) atomicAdd(ta.stats + 1, (unsigned long long)n_scan);
+    }
+}
+
+// The list walk (scenes of at most 8 spheres, or without a tree): geometry in LDS or by scalar loads,
+// as feature_kernel.
+template <bool kLds>
+__global__ __launch_bounds__(kBlock) void trace_kernel(KernelParams p, const GeoRec* __restrict__ geo_g,
+                                                       const MatRec* __restrict__ mat_g, TraceArgs ta) {
+    extern __shared__ GeoRec lds_geo[];
+    const GeoRec* geo = geo_g;
+    if constexpr (kLds) {
+        for (uint32_t k = threadIdx.x; k < p.n_pad; k += blockDim.x) lds_geo[k] = geo_g[k];
+        __syncthreads();
+        geo = lds_geo;
+    }
+    trace_loop<false>(p, LinearWalker<4>{geo, p.n_pad, p.n_spheres}, geo_g, mat_g, ta, 0.0);
+}
+
+// The BVH walk, the tree staged as feature_kernel_bvh stages it.  KernelParams and BvhArgs are the
+// first two arguments: the walker reads the always-list from the kernarg segment at their offsets.
+template <bool kLdsScene>
+__global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) void trace_kernel_bvh(
+    KernelParams p, BvhArgs b, const GeoRec* __restrict__ geo_g, const MatRec* __restrict__ mat_g, TraceArgs ta) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const size_t scene_bytes = kLdsScene ? (size_t)bvh_leaves_offset(b.n_nodes) + (size_t)b.n_leaves * sizeof(BvhLeaf) : 0;
+    using Stack = std::conditional_t<kLdsScene, StackEntry, int32_t>;
+    using Walker = BvhWalker<kLdsScene, kBlockBvh, Stack, false>;
+    Stack* stack = (Stack*)(lds_raw + scene_bytes);
+    stack[threadIdx.x] = (Stack)Walker::kEnd;  // entry 0 of this lane's stack: popping it ends the walk
+    const BvhNode* nodes = b.nodes;
+    const BvhLeaf* leaves = b.leaves;
+    if constexpr (kLdsScene) {
+        BvhNode* ln = (BvhNode*)lds_raw;
+        BvhLeaf* ll = (BvhLeaf*)(lds_raw + bvh_leaves_offset(b.n_nodes));
+        for (uint32_t k = threadIdx.x; k < b.n_nodes; k += blockDim.x) ln[k] = b.nodes[k];
+        for (uint32_t k = threadIdx.x; k < b.n_leaves; k += blockDim.x) ll[k] = b.leaves[k];
+        __syncthreads();
+        nodes = ln;
+        leaves = ll;
+    }
+    trace_loop<true>(p, Walker{nodes, leaves, b.always_geo, b.always_sid, b.n_always, stack + threadIdx.x, b.origin_bound,
+                               geo_g, p.n_pad
+#if RTZIG_BOUNDS
+                               , b.n_nodes * (uint32_t)sizeof(BvhNode), (uint32_t)(b.n_leaves * sizeof(BvhLeaf)), b.stack_depth, ta.ctr
+#endif
+                     }, geo_g, mat_g, ta, (double)b.origin_bound);
+}
+
 // Direct mode's second pass (rt_kernel.h "Work units"): thread q adds pixel q's stored colors in
 // sample order — pixelColor += rayColor(ray), camera.zig:133-136, from pixelColor = 0 — then
 // scales (:137) and writes linear f64 or the fused Color.toRgb bytes.  A wave's loads of one sample
@@ -2870,6 +3009,54 @@ extern "C" hipError_t rtk_launch_features(const rtk::KernelParams* p, const rtk:
     RTK_FEAT(0) RTK_FEAT(2) RTK_FEAT(4)
 #undef RTK_FEAT
     return hipErrorInvalidValue;
+}
+
+// Ray queries: the trace kernel of the structure rtk_launch_features would walk — `b` == nullptr: the
+// list (the variant variant_choice picks); else the tree, in LDS under the same bvh_lds_plan rule —
+// over tiles of 64 rays, a wave each; the grid as the feature launcher sizes it.
+extern "C" hipError_t rtk_launch_trace(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                       const rtk::MatRec* mat, const rtk::TraceArgs* ta, hipStream_t stream,
+                                       const char** name) {
+    using namespace rtk;
+    if (ta->n_rays == 0) return hipSuccess;
+    if (ta->ray_stride < 3 || !ta->origins || !ta->directions) return hipErrorInvalidValue;
+    TraceArgs a = *ta;
+    a.n_tiles = (uint32_t)(((uint64_t)a.n_rays + 63) / 64);
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+        cus = 256;
+    // blocks: a wave per tile, at least one block per CU while tiles last, at most the resident grid
+    auto grid_of = [&](uint32_t block, uint64_t cap) {
+        const uint64_t need = ((uint64_t)a.n_tiles + block / 64 - 1) / (block / 64);
+        const uint64_t spread = a.n_tiles < (uint32_t)cus ? a.n_tiles : (uint64_t)cus;
+        const uint64_t g = need > spread ? need : spread;
+        return (uint32_t)(g < cap ? g : cap);
+    };
+    if (b == nullptr) {
+        const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
+        const size_t shmem = list_walk_lds(v.lds, p->n_pad, false);  // no seed window
+        auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+            const uint64_t cap = persistent_blocks(kernel, shmem);
+            if (name) *name = nm;
+            hipLaunchKernelGGL(kernel, dim3(grid_of(kBlock, cap)), dim3(kBlock), shmem, stream, *p, geo, mat, a);
+            return hipGetLastError();
+        };
+        return v.lds ? launch(trace_kernel<true>, "lds_u4(trace)") : launch(trace_kernel<false>, "smem_u4(trace)");
+    }
+    if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
+    const uint32_t block = (uint32_t)kBlockBvh;
+    const auto [lds_scene, scene_bytes, stack_bytes] = bvh_lds_plan(b->n_nodes, b->n_leaves, b->stack_depth, block, kLdsSceneBudget);
+    const size_t shmem = (lds_scene ? scene_bytes : 0) + stack_bytes;
+    auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+        uint32_t cap32 = 0;
+        const hipError_t ea = rtk_resident_blocks((const void*)kernel, (int)block, shmem, &cap32);
+        if (ea != hipSuccess) return ea;
+        if (name) *name = nm;
+        hipLaunchKernelGGL(kernel, dim3(grid_of(block, cap32)), dim3(block), shmem, stream, *p, *b, geo, mat, a);
+        return hipGetLastError();
+    };
+    return lds_scene ? launch(trace_kernel_bvh<true>, "bvh_lds(trace)") : launch(trace_kernel_bvh<false>, "bvh_global(trace)");
 }
 
 extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, hipStream_t stream) {

@@ -156,6 +156,7 @@ struct rt_context {
     bool profile = false;  // instrumented kernels: d_stats must hold RT_PROFILE_STATS_WORDS uint64 (rt.h)
     int precision = RT_PRECISION_F64;
     std::vector<hipEvent_t> events;  // kEventsPerCall per timed slot (open_call)
+    std::vector<uint8_t> no_reduce;  // per timed slot: 1 when the call says its reduce time is exactly 0 (rt_trace_rays)
     uint32_t call_first = 0;
     uint32_t timed_calls = 0;
     uint32_t log_used = 0;
@@ -509,6 +510,8 @@ int open_call(rt_context* ctx, hipStream_t s, uint32_t n_slots, hipEvent_t** ev)
             ctx->events.push_back(e);
         }
         ctx->timed_calls = n_slots;
+        ctx->no_reduce.resize(ctx->events.size() / kEventsPerCall, 0);
+        for (uint32_t k = 0; k < n_slots; k++) ctx->no_reduce[ctx->call_first + k] = 0;
         *ev = &ctx->events[kEventsPerCall * ctx->call_first];
     }
     if (ctx->launched_valid && ctx->launched_stream != s) HIP_CHECK(hipStreamWaitEvent(s, ctx->launched, 0));
@@ -1028,6 +1031,83 @@ int rt_render_rows_features(rt_context* ctx, const rt_camera* cam, uint32_t row0
     return close_call(ctx, s, ev);
 }
 
+// ---- ray queries (rt.h) ----------------------------------------------------------
+// One launch of the trace kernel of the structure the context holds (use_bvh, as
+// rt_context_tree_info reports it), always in parity arithmetic; no workspace, no training.
+int rt_trace_rays(rt_context* ctx, const void* d_origins, const void* d_directions, uint32_t ray_stride,
+                  uint64_t n_rays, double t_min, double t_max, const void* d_intervals, const rt_ray_hits* out,
+                  void* d_stats, void* stream) {
+    // the argument checks that need no context come first, the context last: each answers before
+    // anything touches a device
+    if (!d_origins) { rt_set_last_error("null d_origins"); return RT_ERR_INVALID; }
+    if (!d_directions) { rt_set_last_error("null d_directions"); return RT_ERR_INVALID; }
+    if (!out) { rt_set_last_error("null out"); return RT_ERR_INVALID; }
+    if (ray_stride == 1 || ray_stride == 2) { rt_set_last_error("ray_stride must be 0 or at least 3"); return RT_ERR_INVALID; }
+    if (n_rays >= (1ull << 32)) { rt_set_last_error("n_rays must be below 2^32"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (n_rays == 0) return RT_OK;
+    if (!out->index && !out->t && !out->point && !out->normal && !out->front && !d_stats) return RT_OK;  // no launch
+    if (ctx->n_spheres == 0) { rt_set_last_error("no scene uploaded"); return RT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    if (!rc) rc = ensure_counters(ctx, s);
+    if (rc) return rc;
+    const bool bvh = use_bvh(ctx);
+    rtk::KernelParams p;
+    std::memset(&p, 0, sizeof p);
+    p.n_spheres = ctx->n_spheres;
+    p.n_pad = (ctx->n_spheres + rtk::kPad - 1) / rtk::kPad * rtk::kPad;
+    rtk::TraceArgs ta{};
+    ta.origins = (const double*)d_origins;
+    ta.directions = (const double*)d_directions;
+    ta.intervals = (const double*)d_intervals;
+    ta.index = out->index;
+    ta.t = out->t;
+    ta.point = out->point;
+    ta.normal = out->normal;
+    ta.front = out->front;
+    ta.stats = (unsigned long long*)d_stats;
+    ta.ctr = ctx->d_ctr;
+    ta.t_min = t_min;
+    ta.t_max = t_max;
+    ta.n_rays = (uint32_t)n_rays;
+    ta.ray_stride = ray_stride ? ray_stride : 3;
+    hipEvent_t* ev = nullptr;
+    rc = open_call(ctx, s, 1, &ev);
+    if (rc) return rc;
+    if (ev) {
+        HIP_CHECK(hipEventRecord(ev[0], s));
+        ctx->no_reduce[ctx->call_first] = 1;  // no reduce pass: reduce_ms is 0, not the gap between two events
+    }
+    HIP_CHECK(rtk_launch_trace(&p, bvh ? &ctx->bvh : nullptr, ctx->d_geo, ctx->d_mat, &ta, s, &ctx->last_kernel));
+    return close_call(ctx, s, ev);
+}
+
+int rt_context_origin_bound(rt_context* ctx, double* bound) {
+    if (!ctx || !bound) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
+    // the bound the kernels compare with: the builder's, rounded down to f32 (upload_bvh)
+    *bound = ctx->n_spheres && use_bvh(ctx) ? (double)ctx->bvh.origin_bound : 0.0;
+    return RT_OK;
+}
+
+// prepare_tree's far-camera path for a bound the caller names: the SAH tree rebuilt with box padding
+// for origins up to bound * 1.01.  Any tree gives the same bits; a trained tree is dropped.
+int rt_context_reserve_origin_bound(rt_context* ctx, double bound) {
+    if (!(bound > 0 && bound * 1.01 < HUGE_VAL)) { rt_set_last_error("bound must be finite and > 0"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (ctx->n_spheres == 0) { rt_set_last_error("no scene uploaded"); return RT_ERR_INVALID; }
+    if (!ctx->scene.bvh_ok || bound <= (double)ctx->bvh.origin_bound) return RT_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = quiesce(ctx);
+    if (rc) return rc;
+    build_bvh(ctx->scene, bound * 1.01);
+    rc = upload_bvh(ctx);
+    if (rc) return rc;
+    trace_mark("bvh_rebuild_reserved_bound");
+    return RT_OK;
+}
+
 // ---- adaptive sampling (rt.h) ---------------------------------------------------
 // A gather pass: direct mode over the listed pixels, in as many sub-passes as the sample buffer's cap
 // asks for.  Every sub-pass is a gather sample kernel (which reads each pixel's count for its stream
@@ -1444,7 +1524,7 @@ static int sum_times(rt_context* ctx, uint32_t first, uint32_t count, double* sa
         const hipEvent_t* e = &ctx->events[kEventsPerCall * c];  // start, sample kernel done, reduce start, end
         HIP_CHECK(hipEventSynchronize(e[3]));
         HIP_CHECK(hipEventElapsedTime(&a, e[0], e[1]));
-        HIP_CHECK(hipEventElapsedTime(&b, e[2], e[3]));
+        if (!ctx->no_reduce[c]) HIP_CHECK(hipEventElapsedTime(&b, e[2], e[3]));
         sm += a;
         rm += b;
     }

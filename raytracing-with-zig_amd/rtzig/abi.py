@@ -132,7 +132,19 @@ class RtTemporalParams(C.Structure):
     ]
 
 
+class RtRayHits(C.Structure):
+    """rt_ray_hits: the device output pointers of rt_trace_rays (rt.h); each may be None (skipped)."""
+    _fields_ = [
+        ("index", C.c_void_p),
+        ("t", C.c_void_p),
+        ("point", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("front", C.c_void_p),
+    ]
+
+
 DENOISE_PARAMS_SIZE = 56
+RAY_HITS_SIZE = 40
 TEMPORAL_FRAME_SIZE = 64
 TEMPORAL_PARAMS_SIZE = 48
 SPHERE_SIZE = 80

@@ -65,6 +65,11 @@ class Scene:
         self.world = _concat(self.world, (RtSphere * 1)(s))
         return self
 
+    def hit(self, origins, directions, t_min=1e-3, t_max=INF, intervals=None, device=0):
+        """world.hit (hittable.zig:64-77) for (n, 3) arrays of rays, on the GPU: trace_rays' dict."""
+        return trace_rays(self.world, origins, directions, t_min=t_min, t_max=t_max, intervals=intervals,
+                          device=device)
+
 
 def _concat(a, b):
     out = (RtSphere * (len(a) + len(b)))()
@@ -374,6 +379,57 @@ def render_features(cam, spheres, spp, device=0):
     return {"albedo": res[0], "normal": res[1], "depth": mean_depth, "coverage": cnt / float(spp), "hits": cnt}
 
 
+def trace_rays(spheres, origins, directions, t_min=1e-3, t_max=INF, intervals=None, device=0):
+    """HittableList.hit of caller-supplied rays on one GPU (rt_trace_rays), bit for bit the reference's
+    f64 result.  origins, directions: (n, 3) arrays; intervals: None or (n, 2), per-ray (t_min, t_max).
+    Returns a dict of numpy arrays:
+        index  (n,)   i32  the sphere hit (its index in `spheres`), -1 on a miss
+        t      (n,)   f64  the accepted root, inf on a miss
+        point  (n, 3) f64  origin + direction * t, 0 on a miss
+        normal (n, 3) f64  the normal after setFaceNormal, 0 on a miss
+        front  (n,)   bool the ray hit the outside of the sphere"""
+    import torch
+
+    o = np.ascontiguousarray(origins, np.float64)
+    d = np.ascontiguousarray(directions, np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both be (n, 3)")
+    n = o.shape[0]
+    iv = None
+    if intervals is not None:
+        iv = np.ascontiguousarray(intervals, np.float64)
+        if iv.shape != (n, 2):
+            raise ValueError("intervals must be (n, 2)")
+    if n == 0:
+        return {"index": np.zeros(0, np.int32), "t": np.zeros(0), "point": np.zeros((0, 3)),
+                "normal": np.zeros((0, 3)), "front": np.zeros(0, bool)}
+    ns = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * ns)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_o = torch.from_numpy(o).to(dev)
+            d_d = torch.from_numpy(d).to(dev)
+            d_iv = torch.from_numpy(iv).to(dev) if iv is not None else None
+            idx = torch.empty(n, dtype=torch.int32, device=dev)
+            t = torch.empty(n, dtype=torch.float64, device=dev)
+            vec = torch.empty((2, n, 3), dtype=torch.float64, device=dev)  # point, normal
+            front = torch.empty(n, dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            r.trace_rays(d_o.data_ptr(), d_d.data_ptr(), n, t_min, t_max, idx.data_ptr(), t.data_ptr(),
+                         vec[0].data_ptr(), vec[1].data_ptr(), front.data_ptr(),
+                         d_intervals_ptr=d_iv.data_ptr() if d_iv is not None else None, stream_ptr=stream)
+            res = {"index": idx.cpu().numpy(), "t": t.cpu().numpy()}  # waits for the stream
+            v = vec.cpu().numpy()
+            res.update(point=v[0], normal=v[1], front=front.cpu().numpy().astype(bool))
+            r.sync()  # reports a failure the kernel recorded
+    finally:
+        r.close()
+    return res
+
+
 def denoise_params(**overrides):
     """rt_denoise_params: the library's defaults (rt_denoise_default_params: levels 2, sigma_l 4,
     sigma_n 32, sigma_a 32, sigma_z 0.05, sigma_h 4, epsilon 1e-6) with the given fields replaced."""
@@ -646,6 +702,32 @@ class DeviceRenderer:
                                                sample_count, C.c_void_p(d_albedo_ptr or 0),
                                                C.c_void_p(d_normal_ptr or 0), C.c_void_p(d_depth_ptr or 0),
                                                C.c_void_p(d_hits_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def trace_rays(self, d_origins_ptr, d_directions_ptr, n_rays, t_min=1e-3, t_max=INF, d_index_ptr=None,
+                   d_t_ptr=None, d_point_ptr=None, d_normal_ptr=None, d_front_ptr=None, d_intervals_ptr=None,
+                   d_stats_ptr=None, ray_stride=3, stream_ptr=None):
+        """rt_trace_rays: HittableList.hit of n_rays rays on the device, bit for bit.  Origins and
+        directions are f64, ray q at [q * ray_stride + 0..2]; d_intervals_ptr (n x 2 f64) replaces
+        (t_min, t_max) per ray.  Outputs, each skipped when None: index (n i32, -1: miss), t (n f64, inf:
+        miss), point and normal (n x 3 f64), front (n u8).  d_stats_ptr: 2 x u64, incremented by {rays,
+        rays answered by the list scan}.  Always parity arithmetic."""
+        hits = abi.RtRayHits(d_index_ptr or None, d_t_ptr or None, d_point_ptr or None, d_normal_ptr or None,
+                             d_front_ptr or None)
+        check("rt_trace_rays",
+              self.lib.rt_trace_rays(self.ctx, C.c_void_p(d_origins_ptr or 0), C.c_void_p(d_directions_ptr or 0),
+                                     ray_stride, n_rays, t_min, t_max, C.c_void_p(d_intervals_ptr or 0),
+                                     C.byref(hits), C.c_void_p(d_stats_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def origin_bound(self):
+        """rt_context_origin_bound: rays starting within it (max |o_k|) may use the tree; 0: the list walk."""
+        b = C.c_double()
+        check("rt_context_origin_bound", self.lib.rt_context_origin_bound(self.ctx, C.byref(b)))
+        return b.value
+
+    def reserve_origin_bound(self, bound):
+        """rt_context_reserve_origin_bound: rebuilds the tree for ray origins up to `bound` (no result bit
+        changes; a trained tree is dropped)."""
+        check("rt_context_reserve_origin_bound", self.lib.rt_context_reserve_origin_bound(self.ctx, float(bound)))
 
     def _pixel_list(self, cam, pixels, n_pixels):
         """(device pointer, length) of a pixel list for accumulate_pixels.  None: every pixel.  An int is

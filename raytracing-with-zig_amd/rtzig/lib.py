@@ -6,7 +6,7 @@ render call goes through the HIP kernel on a gfx950 device (rt_render / rt_rende
 import ctypes as C
 import os
 
-from .abi import (RtCamera, RtCameraParams, RtDenoiseParams, RtOptions, RtSphere, RtTemporalFrame,
+from .abi import (RtCamera, RtCameraParams, RtDenoiseParams, RtOptions, RtRayHits, RtSphere, RtTemporalFrame,
                   RtTemporalParams)
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +31,9 @@ EXPORTED = [
     "rt_denoise",
     "rt_temporal_default_params",
     "rt_temporal_accumulate",
+    "rt_trace_rays",
+    "rt_context_origin_bound",
+    "rt_context_reserve_origin_bound",
     "rt_context_flush",
     "rt_context_fold_pending",
     "rt_kernel_name",
@@ -97,6 +100,10 @@ def _declare(lib):
         "rt_temporal_default_params": (C.c_int, [P(RtTemporalParams)]),
         "rt_temporal_accumulate": (C.c_int, [vp, P(RtCamera), P(RtTemporalFrame), P(RtCamera), P(RtTemporalFrame),
                                              P(RtTemporalParams), vp, vp]),
+        "rt_trace_rays": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_double, C.c_double, vp, P(RtRayHits),
+                                    vp, vp]),
+        "rt_context_origin_bound": (C.c_int, [vp, P(C.c_double)]),
+        "rt_context_reserve_origin_bound": (C.c_int, [vp, C.c_double]),
         "rt_context_flush": (C.c_int, [vp]),
         "rt_context_fold_pending": (C.c_int, [vp, P(C.c_int)]),
         "rt_kernel_name": (C.c_char_p, [vp]),

@@ -31,6 +31,10 @@
 #              colour pass on the same rays, on config 4's image and the 400x225 chapter-13 image
 #              (tools/feature_cost.py; its JSON on stdout is kept as profiles/features/cost.json).  Its
 #              GPU tests (tests/test_gpu_features.py) run with the `tests` step
+#   trace      what a ray query costs: rt_trace_rays on 15.36 M coherent camera rays against the feature
+#              pass at 16 samples plus a copy of the bytes it moves, and the incoherent, far-origin and
+#              tiny-batch figures (tools/trace_cost.py; its JSON on stdout is kept as
+#              profiles/trace/cost.json).  Its GPU tests (tests/test_gpu_trace.py) run with the `tests` step
 #   denoise   what rt_denoise costs against the 16-sample gather pass it stands in for, per level and
 #              kernel form, and the RMSE table against a 500-spp frame, on config 4's image
 #              (tools/denoise_cost.py; the "cost" and "quality" objects of its JSON on stdout are kept
@@ -77,6 +81,7 @@ for step in "$@"; do
     progressive) run progressive 200 python3 -u tools/progressive_cost.py ;;
     adaptive) run adaptive 300 python3 -u tools/adaptive_cost.py ;;
     features) run features 200 python3 -u tools/feature_cost.py ;;
+    trace)   run trace 300 python3 -u tools/trace_cost.py ;;
     denoise) run denoise 300 python3 -u tools/denoise_cost.py ;;
     temporal) run temporal 300 python3 -u tools/temporal_cost.py ;;
     peak)    run peak 300 ./tools/bin/peak_rates ${PEAK_MS:-60} ${PEAK_MODE:-2} ;;
