@@ -3,12 +3,19 @@
 Shared by tests/test_oracle.py (CPU: oracle F's 32-bit instantiation against its 64-bit one) and
 tests/test_fast_oracle.py (GPU: the f32 fast mode against the same pair).  Everything is rendered at
 1 sample per pixel unless stated, so a pixel is one sample's colour.
+
+Also the scene and parameter builders that more than one test file uses: always_list_scene and
+far_origin_scene (tests/test_gpu_parity.py, tests/test_gpu_domain.py) and golden_params, the golden
+test's camera preset (tests/test_oracle.py, tests/test_host.py, tests/test_gpu_parity.py).
 """
+import math
+
 import numpy as np
 
 import rtzig
-from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtSphere
+from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtCameraParams, RtSphere
 
+INF = math.inf
 THETAS = (1e-3, 1e-4, 1e-5)
 INPUT_CAP = 0.01  # share_F32(1e-3) every scene below must stay under (checked on the CPU)
 GPU_CAP = 0.02    # share_gpu(1e-3), whatever F32 says
@@ -87,6 +94,54 @@ def large():
     scene.world = arr
     return (rtzig.Camera.builder(96, 16 / 9).setScene(scene).setDefocusAngle(0.6).setFocusDist(10)
             .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(2).setBounceMax(3).build())
+
+
+def always_list_scene(n_big, ground, n_unbound):
+    """The scene and camera of test_always_list_sizes_bit_exact (64 x 42, 4 spp): a grid of small
+    spheres with n_big radius-1.2 spheres among them, an optional radius-1000 ground and n_unbound
+    spheres centred at 2e30."""
+    rng = np.random.default_rng(100 + 10 * n_big + n_unbound + (5 if ground else 0))
+    sph = []
+    for a in range(-4, 4):
+        for b in range(-4, 4):
+            sph.append(RtSphere(center=D3(a + 0.9 * rng.uniform(), 0.2, b + 0.9 * rng.uniform()), radius=0.2,
+                                material=int(rng.integers(0, 3)), albedo=D3(*rng.uniform(0, 1, 3)),
+                                fuzz=float(rng.uniform(0, 0.5)), refraction_index=1.5))
+    for k in range(n_big):
+        sph.append(RtSphere(center=D3(-3.0 + 2.0 * k, 1.2, 0.3 * k), radius=1.2, material=k % 3,
+                            albedo=D3(0.7, 0.6, 0.5), fuzz=0.0, refraction_index=1.5))
+    if ground:
+        sph.insert(int(rng.integers(0, len(sph))), RtSphere(center=D3(0, -1000, 0), radius=1000.0, material=0,
+                                                            albedo=D3(0.5, 0.5, 0.5)))
+    for k in range(n_unbound):
+        sph.insert(int(rng.integers(0, len(sph))), RtSphere(center=D3(2e30, 1.0 + k, 0), radius=1.0, material=0,
+                                                            albedo=D3(0.5, 0.5, 0.5)))
+    arr = (RtSphere * len(sph))(*sph)
+    scene = rtzig.Scene.init(7)
+    scene.world = arr
+    cam = (rtzig.Camera.builder(64, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10.0)
+           .setViewport((13, 2, 3), (0, 0, 0), 20.0).setSamplesPerPixel(4).build())
+    return arr, cam
+
+
+def far_origin_scene(width=96):
+    """The scene and camera of test_far_origin_lanes_walk_without_culling: the final scene of seed
+    0xfa7 plus an unboundable radius-2e30 metal sphere."""
+    scene = rtzig.Scene.init(0xfa7).generateWorld()
+    huge = RtSphere(center=D3(0, -2e30, 0), radius=2e30, material=RT_METAL, albedo=D3(0.7, 0.7, 0.7), fuzz=0.3)
+    arr = (RtSphere * (len(scene.world) + 1))(*scene.world, huge)
+    scene.world = arr
+    cam = (rtzig.Camera.builder(width, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10)
+           .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(4).build())
+    return arr, cam
+
+
+def golden_params(width=400, aspect=16.0 / 9.0, spp=10, seed=0xDEADBEEF):
+    # main.zig:24-31 preset
+    return RtCameraParams(image_width=width, samples_per_pixel=spp, bounce_max=50,
+                          aspect_ratio=aspect, look_from=D3(13, 2, 3), look_at=D3(0, 0, 0),
+                          v_up=D3(0, 1, 0), vfov=20, defocus_angle=0.6, focus_dist=10,
+                          t_min=1e-3, t_max=INF, seed=seed)
 
 
 def with_camera(cam, **fields):

@@ -4,42 +4,19 @@ argument check that can answer without a device does, the ABI version did not mo
 kernels exist within their register budget (checked at build time, as tests/test_kernel_resources.py
 does for the kernels they are twins of), and render_adaptive validates its arguments on the host."""
 import ctypes as C
-import os
 import re
-import sys
 
 import pytest
 
 import rtzig
-from rtzig.abi import RtCamera
-from rtzig.lib import EXPORTED
+from abi_support import assert_bound, assert_invalid, cam_of, resources, vp
 
-RT_ERR_INVALID = -1
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_build  # noqa: E402
 NAN = float("nan")
 
 
-def vp(buf):
-    return C.cast(buf, C.c_void_p)
-
-
-def cam_of(w=4, h=3):
-    """A camera that passes validate_camera (finite vectors), w x h pixels."""
-    cam = RtCamera()
-    cam.image_width, cam.image_height, cam.samples_per_pixel, cam.bounce_max = w, h, 1, 1
-    cam.pixel_samples_scale = 1.0
-    cam.t_min, cam.t_max = 1e-3, float("inf")
-    return cam
-
-
 def test_symbols_exported_and_bound():
-    lib = rtzig.load()
     for name, n_args in (("rt_render_pixels_accumulate", 10), ("rt_accum_select", 13), ("rt_accum_resolve_counts", 7)):
-        assert name in EXPORTED
-        fn = getattr(lib, name)
-        assert fn.restype is C.c_int and len(fn.argtypes) == n_args
+        assert_bound(name, n_args)
     for name in ("render_adaptive",):
         assert name in rtzig.__all__ and callable(getattr(rtzig, name))
     for name in ("accumulate_pixels", "select", "resolve_counts"):
@@ -73,8 +50,7 @@ def pixels_call(ctx=None, cam="ok", pixels=None, n_pixels=12, count=1, accum="ok
     (dict(cam=cam_of(0, 3)), b"image_width"),
 ], ids=["ctx", "cam", "accum", "counts", "null-list-short", "null-list-empty", "too-many", "empty-image"])
 def test_pixels_accumulate_invalid_arguments(kw, word):
-    assert pixels_call(**kw) == RT_ERR_INVALID
-    assert word in rtzig.load().rt_last_error()
+    assert_invalid(pixels_call(**kw), word)
 
 
 # ---- rt_accum_select -------------------------------------------------------------------------------
@@ -99,16 +75,14 @@ def select_call(ctx=None, null=None, n=4, min_count=2, max_count=8, tolerance=0.
 ], ids=["ctx", "accum", "m2", "counts", "list", "n", "min1", "min0", "max<min", "n>=2^32", "floor0", "floor<0",
         "floor-nan", "tol-nan"])
 def test_select_invalid_arguments(kw, word):
-    assert select_call(**kw) == RT_ERR_INVALID
-    assert word in rtzig.load().rt_last_error()
+    assert_invalid(select_call(**kw), word)
 
 
 # ---- rt_accum_resolve_counts -----------------------------------------------------------------------
 def test_resolve_counts_null_context_is_invalid():
     lib = rtzig.load()
     a, o, c = (C.c_double * 3)(), (C.c_double * 3)(), (C.c_uint32 * 1)()
-    assert lib.rt_accum_resolve_counts(None, vp(a), vp(c), 1, 0, vp(o), None) == RT_ERR_INVALID
-    assert b"context" in lib.rt_last_error()
+    assert_invalid(lib.rt_accum_resolve_counts(None, vp(a), vp(c), 1, 0, vp(o), None), b"context")
 
 
 # ---- render_adaptive's host-side argument checks ---------------------------------------------------
@@ -124,12 +98,8 @@ def test_render_adaptive_rejects_bad_arguments_before_any_device_work(kw):
 
 
 # ---- the gather kernels' register budget (build time) ----------------------------------------------
-def _resources():
-    return kernel_build.resources("rt_kernel.hip")
-
-
 def test_six_gather_kernels_no_scratch_lds_tree_ones_at_four_waves():
-    rows = _resources()
+    rows = resources("rt_kernel.hip")
     gather = {k: v for k, v in rows.items() if re.search(r"gather_kernel(_bvh|_fast)?I", k)}
     # the list walk (lds, smem), the BVH walk and the fast walk (LDS tree, global-memory tree)
     assert len(gather) == 6, sorted(gather)

@@ -8,32 +8,24 @@ import ctypes as C
 import inspect
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 import denoise_ref
 import rtzig
-from rtzig.abi import RtCamera, RtDenoiseParams
-from rtzig.lib import EXPORTED
+from abi_support import RT_ERR_INVALID, ROOT, assert_bound, assert_invalid, cam_of, resources
+from rtzig.abi import RtDenoiseParams
 
-RT_ERR_INVALID = -1
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_build  # noqa: E402
 DEFAULTS = dict(levels=2, reserved=0, sigma_l=4.0, sigma_n=32.0, sigma_a=32.0, sigma_z=0.05, sigma_h=4.0,
                 epsilon=1e-6)
 
 
 def test_symbols_exported_bound_and_declared():
-    lib = rtzig.load()
     with open(os.path.join(ROOT, "include", "rt.h")) as f:
         header = f.read()
     for name, nargs in (("rt_denoise", 16), ("rt_denoise_default_params", 1)):
-        assert name in EXPORTED
-        fn = getattr(lib, name)
-        assert fn.restype is C.c_int and len(fn.argtypes) == nargs
+        assert_bound(name, nargs)
         assert re.search(r"\bint %s\(" % name, header)
     assert "typedef struct rt_denoise_params" in header
 
@@ -61,10 +53,10 @@ def denoise_call(ctx=None, width=4, height=3, accum=1, m2=1, counts=1, albedo=0,
                  feature_samples=0, params=None, fmt=0, out=1, var_out=0):
     """rt_denoise with made-up non-null pointers (never dereferenced: a null context answers last)."""
     lib = rtzig.load()
-    vp = C.c_void_p
-    return lib.rt_denoise(ctx, width, height, vp(accum * 4096), vp(m2 * 4096), vp(counts * 4096), vp(albedo * 4096),
-                          vp(normal * 4096), vp(depth * 4096), vp(hits * 4096), feature_samples,
-                          C.byref(params) if params is not None else None, fmt, vp(out * 4096), vp(var_out * 4096),
+    p = C.c_void_p
+    return lib.rt_denoise(ctx, width, height, p(accum * 4096), p(m2 * 4096), p(counts * 4096), p(albedo * 4096),
+                          p(normal * 4096), p(depth * 4096), p(hits * 4096), feature_samples,
+                          C.byref(params) if params is not None else None, fmt, p(out * 4096), p(var_out * 4096),
                           None)
 
 
@@ -100,16 +92,14 @@ def test_invalid_arguments_answer_without_a_device(kw, word):
     kw = dict(kw)
     if "params" in kw:
         kw["params"] = rtzig.denoise_params(**kw["params"])
-    assert denoise_call(**kw) == RT_ERR_INVALID
-    assert word in rtzig.load().rt_last_error()
+    assert_invalid(denoise_call(**kw), word)
 
 
 def test_limits_that_pass_the_checks():
     """levels == 16, a zero sigma and 2^32 - 65536 pixels are allowed: the null context answers instead."""
     for kw in (dict(params=rtzig.denoise_params(levels=16, sigma_l=0.0, sigma_z=0.0)),
                dict(width=65535, height=65536)):
-        assert denoise_call(**kw) == RT_ERR_INVALID
-        assert b"context" in rtzig.load().rt_last_error()
+        assert_invalid(denoise_call(**kw), b"context")
 
 
 def test_python_entry_points_and_signatures():
@@ -136,28 +126,18 @@ def test_python_entry_points_and_signatures():
         "on_round"]
 
 
-def _cam(w=4, h=3):
-    cam = RtCamera()
-    cam.image_width, cam.image_height, cam.samples_per_pixel, cam.bounce_max = w, h, 1, 1
-    return cam
-
-
 @pytest.mark.parametrize("kw", [dict(spp=1), dict(spp=0), dict(spp=-3), dict(spp=2 ** 32), dict(spp=4, feature_spp=0),
                                 dict(spp=4, feature_spp=-1), dict(spp=4, output="hdr"),
                                 dict(spp=4, adaptive=dict(max_spp=8)), dict(spp=4, adaptive=dict(max_spp=2, step=1, tolerance=0.1)),
                                 dict(spp=4, adaptive=dict(max_spp=8, step=1, tolerance=0.1, ceiling=1))])
 def test_render_denoised_rejects_bad_arguments_before_any_device_work(kw):
     with pytest.raises(ValueError):
-        rtzig.render_denoised(_cam(), [], **kw)  # an empty scene: never reached
+        rtzig.render_denoised(cam_of(), [], **kw)  # an empty scene: never reached
 
 
 # ---- the denoise kernels' resources (build time) ----------------------------------------------------
-def _resources():
-    return kernel_build.resources("rt_denoise.hip")
-
-
 def test_denoise_kernels_exist_without_scratch_outside_the_other_counts():
-    rows = _resources()
+    rows = resources("rt_denoise.hip")
     assert rows and all("denoise_" in k for k in rows), sorted(rows)  # the translation unit holds nothing else
     for stage in ("denoise_prepare_kernel", "denoise_prefilter_kernel", "denoise_level_tile_kernel",
                   "denoise_level_direct_kernel"):

@@ -2,7 +2,6 @@
 the final gather to rank 0.  Each rank renders its rows with a CPU stand-in (oracle B — tests only,
 the product renders on the GPU); the gathered image must equal the single-rank image bit-for-bit."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -11,15 +10,8 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from ports import free_port
 from rtzig import dist as rdist
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, q):
@@ -50,7 +42,7 @@ def test_gloo_row_interleave_gather(oracle, world):
     import rtzig
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -136,7 +128,7 @@ def test_world1_collective_gather_goes_through_the_group():
     1-rank group (a new buffer), not the world-1 shortcut that returns the local rows."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    p = ctx.Process(target=_one_rank_collective, args=(_free_port(), q))
+    p = ctx.Process(target=_one_rank_collective, args=(free_port(), q))
     p.start()
     copied, equal = q.get(timeout=120)
     p.join(timeout=60)

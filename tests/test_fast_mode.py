@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import rtzig
+from gpu_support import renderers  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,7 +20,7 @@ def box8(x):
     return x[:h, :w].reshape(h // 8, 8, w // 8, 8, 3).mean(axis=(1, 3))
 
 
-def rmse(a, b):
+def box8_rmse(a, b):
     return float(np.sqrt(((box8(a) - box8(b)) ** 2).mean()))
 
 
@@ -35,9 +36,9 @@ def check_stat(cam):
     f64_a = render_rgb(cam, "f64", seed=0xDEADBEEF)
     f64_b = render_rgb(cam, "f64", seed=0x5EED5EED)
     f32_a = render_rgb(cam, "f32", seed=0xDEADBEEF)
-    floor = rmse(f64_a, f64_b)
+    floor = box8_rmse(f64_a, f64_b)
     mean_d = np.abs(f32_a.mean(axis=(0, 1)) - f64_a.mean(axis=(0, 1))).max()
-    err = rmse(f32_a, f64_a)
+    err = box8_rmse(f32_a, f64_a)
     assert mean_d <= 1.0, (mean_d, floor, err)
     assert err <= 1.5 * floor + 0.25, (mean_d, floor, err)
     return floor, err
@@ -72,19 +73,17 @@ def test_fast_vs_reference_golden(golden_dir):
     _, _, gold = read_ppm(open(os.path.join(golden_dir, "chapter14.ppm"), "rb").read())
     b = gold.astype(np.float64)
     assert np.abs(a.mean(axis=(0, 1)) - b.mean(axis=(0, 1))).max() <= 1.0
-    assert rmse(a, b) <= 2.0
+    assert box8_rmse(a, b) <= 2.0
 
 
 @pytest.mark.parametrize("mode", ["ring", "direct"])
-def test_fast_counts_deterministic_and_row_invariant(mode, monkeypatch):
+def test_fast_counts_deterministic_and_row_invariant(mode, monkeypatch, renderers):
     """Every sample is written once; the image does not depend on the row partition or on the unit
     mode (both add each pixel's samples in sample order)."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = rtzig.final_scene_camera(width=240, aspect_ratio=1.5, spp=16)
     H, W = cam.height, cam.width
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
-    r.set_precision("f32")
+    r = renderers(cam, "f32")
     full = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
     st = torch.zeros(2, dtype=torch.int64, device="cuda:0")
     r.render_rows_async(cam.cam, full.data_ptr(), d_stats_ptr=st.data_ptr())

@@ -7,35 +7,15 @@ import ctypes as C
 import inspect
 import os
 import re
-import sys
 
 import pytest
 
 import rtzig
-from rtzig.abi import RtCamera
-from rtzig.lib import EXPORTED
-
-RT_OK = 0
-RT_ERR_INVALID = -1
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_build  # noqa: E402
-
-
-def cam_of(w=4, h=3):
-    """A camera that passes validate_camera (finite vectors), w x h pixels."""
-    cam = RtCamera()
-    cam.image_width, cam.image_height, cam.samples_per_pixel, cam.bounce_max = w, h, 1, 1
-    cam.pixel_samples_scale = 1.0
-    cam.t_min, cam.t_max = 1e-3, float("inf")
-    return cam
+from abi_support import ROOT, assert_bound, assert_invalid, cam_of, resources, vp
 
 
 def test_symbol_exported_and_bound():
-    lib = rtzig.load()
-    assert "rt_render_rows_features" in EXPORTED
-    fn = lib.rt_render_rows_features
-    assert fn.restype is C.c_int and len(fn.argtypes) == 12
+    assert_bound("rt_render_rows_features", 12)
     with open(os.path.join(ROOT, "include", "rt.h")) as f:
         assert re.search(r"\bint rt_render_rows_features\(", f.read())
 
@@ -49,8 +29,7 @@ def features_call(ctx=None, cam="ok", row0=0, row_step=1, n_rows=3, begin=0, cou
     a, n, d, h = (C.c_double * 36)(), (C.c_double * 36)(), (C.c_double * 12)(), (C.c_uint32 * 12)()
     camera = cam_of() if cam == "ok" else cam
     return lib.rt_render_rows_features(ctx, C.byref(camera) if camera is not None else None, row0, row_step, n_rows,
-                                       begin, count, C.cast(a, C.c_void_p), C.cast(n, C.c_void_p),
-                                       C.cast(d, C.c_void_p), C.cast(h, C.c_void_p), None)
+                                       begin, count, vp(a), vp(n), vp(d), vp(h), None)
 
 
 @pytest.mark.parametrize("kw, word", [
@@ -67,14 +46,12 @@ def features_call(ctx=None, cam="ok", row0=0, row_step=1, n_rows=3, begin=0, cou
 ], ids=["ctx", "ctx-empty-samples", "ctx-empty-rows", "cam", "rows-past", "row0-past", "stride-past", "range-end",
         "range-count", "empty-image"])
 def test_invalid_arguments_answer_without_a_device(kw, word):
-    assert features_call(**kw) == RT_ERR_INVALID
-    assert word in rtzig.load().rt_last_error()
+    assert_invalid(features_call(**kw), word)
 
 
 def test_largest_sample_range_passes_the_range_check():
     """sample_begin + sample_count == 2^32 - 1 is allowed: the null context answers instead."""
-    assert features_call(begin=2 ** 32 - 2, count=1) == RT_ERR_INVALID
-    assert b"context" in rtzig.load().rt_last_error()
+    assert_invalid(features_call(begin=2 ** 32 - 2, count=1), b"context")
 
 
 def test_python_entry_points_and_signatures():
@@ -97,12 +74,8 @@ def test_render_features_rejects_bad_sample_counts_before_any_device_work(spp):
 
 
 # ---- the feature kernels' register budget (build time) ---------------------------------------------
-def _resources():
-    return kernel_build.resources("rt_kernel.hip")
-
-
 def test_twelve_feature_kernels_no_scratch_bvh_ones_fit_a_1024_thread_block():
-    rows = _resources()
+    rows = resources("rt_kernel.hip")
     feat = {k: v for k, v in rows.items() if re.search(r"feature_kernel(_bvh)?I", k)}
     # the list walk (lds, smem) and the BVH walk (LDS tree, global-memory tree), each with 1, 4 and 16
     # lanes per pixel

@@ -9,30 +9,14 @@ import pytest
 import torch
 
 import rtzig
+from gpu_support import H37 as H
+from gpu_support import NPIX37 as NPIX
+from gpu_support import W37 as W
+from gpu_support import (DEV, FLOOR, MAX_C, MIN_C, SEL_BLOCK, TOL, Bufs, cam37, list_a, list_b, ref37, select_numpy,
+                         synthetic, unchanged_outside)
+from gpu_support import module_renderers, renderers  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-W, H, NPIX = 37, 20, 740  # 740 pixels: a partial last group of 64
-SEL_BLOCK = 1024          # rtk::kSelBlock, the selection kernels' block size
-
-
-def cam37(spp=1):
-    return rtzig.final_scene_camera(width=W, aspect_ratio=16 / 9, spp=spp)
-
-
-_REF37 = {}
-
-
-def ref37(oracle, n):
-    """Oracle B's (740, 3) image and rays of the 37-wide scene at spp = n (computed once per n)."""
-    if n not in _REF37:
-        cam = cam37(n)
-        img, rays = oracle.render_b(cam.cam, cam.scene.world, threads=16)
-        img = img.reshape(NPIX, 3)
-        img.setflags(write=False)
-        _REF37[n] = (img, rays)
-    return _REF37[n]
 
 
 def expected(oracle, counts):
@@ -40,78 +24,15 @@ def expected(oracle, counts):
     out = np.zeros((NPIX, 3))
     for n in np.unique(counts):
         if n:
-            out[counts == n] = ref37(oracle, int(n))[0][counts == n]
+            out[counts == n] = ref37(oracle, int(n))[0].reshape(NPIX, 3)[counts == n]
     return out
-
-
-def renderer(cam, precision="f64"):
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
-    r.set_precision(precision)
-    return r
-
-
-class Bufs:
-    """The caller's buffers of one image: sums, squared-luminance sums, counts, stats."""
-
-    def __init__(self, n=NPIX, fill=None, m2=True):
-        self.n = n
-        self.accum = torch.empty((n, 3), dtype=torch.float64, device=DEV)
-        self.m2 = torch.empty(n, dtype=torch.float64, device=DEV) if m2 else None
-        if fill is not None:
-            self.accum.fill_(fill)
-            if m2:
-                self.m2.fill_(fill)
-        self.counts = torch.zeros(n, dtype=torch.int32, device=DEV)
-        self.stats = torch.zeros(2, dtype=torch.int64, device=DEV)
-
-    def add(self, r, cam, pixels, count, **kw):
-        r.accumulate_pixels(cam.cam, pixels, count, self.accum.data_ptr(),
-                            self.m2.data_ptr() if self.m2 is not None else None, self.counts.data_ptr(),
-                            d_stats_ptr=self.stats.data_ptr(), **kw)
-
-    def bits(self):
-        """(accum, m2, counts) on the host as integers: NaN-safe bit comparisons."""
-        torch.cuda.synchronize()
-        m2 = self.m2.cpu().numpy().view(np.int64) if self.m2 is not None else None
-        return self.accum.cpu().numpy().view(np.int64), m2, self.counts.cpu().numpy()
-
-    def resolved(self, r, output="linear"):
-        out = torch.empty((self.n, 3), dtype=torch.float64 if output == "linear" else torch.uint8, device=DEV)
-        r.resolve_counts(self.accum.data_ptr(), self.counts.data_ptr(), self.n, out.data_ptr(), output=output)
-        return out.cpu().numpy()
-
-
-def list_a():
-    """Pixels 0, 63, 64, 739 (the ends of the first group of 64, the start of the second, the last
-    pixel) plus every third pixel, shuffled.  Every third pixel from 2 on shares none of the four, so
-    the list has 246 + 4 = 250 pairwise distinct entries (the contract asks for distinct indices)."""
-    a = np.array(sorted({0, 63, 64, 739} | set(range(2, NPIX, 3))))
-    assert len(a) == 250
-    return np.random.default_rng(1).permutation(a)
-
-
-def list_b():
-    """Half overlaps A: every other entry of A plus as many pixels outside A, shuffled."""
-    a = np.sort(list_a())
-    outside = np.setdiff1d(np.arange(NPIX), a)
-    b = np.concatenate([a[::2], outside[::3][:125]])
-    assert len(b) == 250 and len(np.intersect1d(a, b)) == 125
-    return np.random.default_rng(2).permutation(b)
-
-
-def unchanged_outside(before, after, listed):
-    mask = np.ones(NPIX, bool)
-    mask[listed] = False
-    for x, y in zip(before, after):
-        assert np.array_equal(x[mask], y[mask])
 
 
 # ---- 1 ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 7, 48])
-def test_identity_list_equals_oracle(oracle, n):
+def test_identity_list_equals_oracle(oracle, n, renderers):
     cam = cam37()
-    r = renderer(cam)
+    r = renderers(cam)
     b = Bufs()
     b.add(r, cam, None, n)
     img = b.resolved(r)
@@ -120,7 +41,7 @@ def test_identity_list_equals_oracle(oracle, n):
     assert "gather" in r.kernel_name() and "bvh" in r.kernel_name()
     r.close()
     ref, rays = ref37(oracle, n)
-    assert np.array_equal(img, ref)
+    assert np.array_equal(img, ref.reshape(NPIX, 3))
     assert (counts == n).all()
     assert b.stats.cpu().tolist() == [rays, NPIX * n]
 
@@ -147,9 +68,9 @@ def sparse_passes(r, cam, b):
     return want
 
 
-def test_sparse_lists_with_uneven_counts(oracle):
+def test_sparse_lists_with_uneven_counts(oracle, renderers):
     cam = cam37()
-    r = renderer(cam)
+    r = renderers(cam)
     b = Bufs()
     want = sparse_passes(r, cam, b)
     img, rgb = b.resolved(r), b.resolved(r, output="rgb8")
@@ -160,10 +81,10 @@ def test_sparse_lists_with_uneven_counts(oracle):
     assert np.array_equal(rgb, oracle.to_rgb8(ref))
 
 
-def test_fast_mode():
+def test_fast_mode(renderers):
     """RT_PRECISION_F32: every pixel is the one-pass fast render's at its count."""
     cam = cam37()
-    r = renderer(cam, precision="f32")
+    r = renderers(cam, precision="f32")
     b = Bufs()
     want = sparse_passes(r, cam, b)
     assert "fast_f32" in r.kernel_name() and "gather" in r.kernel_name()
@@ -179,9 +100,9 @@ def test_fast_mode():
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------
-def test_list_order_does_not_matter():
+def test_list_order_does_not_matter(renderers):
     cam = cam37()
-    r = renderer(cam)
+    r = renderers(cam)
     A = np.sort(list_a())
     got = []
     for order in (A, A[::-1].copy(), np.random.default_rng(3).permutation(A)):
@@ -198,10 +119,10 @@ def test_list_order_does_not_matter():
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------
-def test_runtime_split(oracle, monkeypatch):
+def test_runtime_split(oracle, monkeypatch, renderers):
     """A cap of 7 samples of the 740 pixels (and a little): 24 samples run as 7 + 7 + 7 + 3."""
     cam = cam37()
-    r = renderer(cam)
+    r = renderers(cam)
     whole = Bufs()
     whole.add(r, cam, None, 24)
     monkeypatch.setenv("RTZIG_GATHER_BYTES", str(NPIX * 24 * 7 + 100))
@@ -212,7 +133,7 @@ def test_runtime_split(oracle, monkeypatch):
     r.enable_timing(False)
     for x, y in zip(whole.bits(), split.bits()):
         assert np.array_equal(x, y)
-    assert np.array_equal(split.resolved(r), ref37(oracle, 24)[0])
+    assert np.array_equal(split.resolved(r), ref37(oracle, 24)[0].reshape(NPIX, 3))
     assert whole.stats.cpu().tolist() == split.stats.cpu().tolist() == [ref37(oracle, 24)[1], NPIX * 24]
     # a sparse list at a cap of exactly one sample of it: 3 sub-passes of 1
     monkeypatch.setenv("RTZIG_GATHER_BYTES", str(250 * 24))
@@ -233,9 +154,9 @@ def test_runtime_split(oracle, monkeypatch):
 
 # ---- 5 ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["ring", "direct"])
-def test_interoperation_with_row_passes(oracle, mode, monkeypatch):
+def test_interoperation_with_row_passes(oracle, mode, monkeypatch, renderers):
     cam = cam37()
-    r = renderer(cam)
+    r = renderers(cam)
     b = Bufs(m2=False)  # row passes keep no m2: the gather pass runs without one
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     r.accumulate(cam.cam, b.accum.data_ptr(), 0, 10)
@@ -253,9 +174,9 @@ def test_interoperation_with_row_passes(oracle, mode, monkeypatch):
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------
-def test_m2_is_bit_exact_and_a_new_pixel_overwrites(oracle):
+def test_m2_is_bit_exact_and_a_new_pixel_overwrites(oracle, renderers):
     cam = cam37()
-    r = renderer(cam)
+    r = renderers(cam)
     # per-sample colours from the existing API: a zeroed accumulator and one sample (0 + c is exact)
     cols = np.zeros((12, NPIX, 3))
     one = torch.empty((NPIX, 3), dtype=torch.float64, device=DEV)
@@ -288,64 +209,9 @@ def test_m2_is_bit_exact_and_a_new_pixel_overwrites(oracle):
 
 
 # ---- 7 ---------------------------------------------------------------------------------------------
-MIN_C, MAX_C, TOL, FLOOR = 4, 32, 0.1, 0.01
-
-
-def synthetic(pattern, n):
-    """(accum (n, 3), m2 (n), counts (n)) on the host.  'quiet' pixels have every sample at luminance
-    0.6 (v rounds to about 0), 'noisy' ones a variance of at least mean^2 (err >= sqrt(1 / 39) > TOL)."""
-    rng = np.random.default_rng(n * 31 + len(pattern))
-    counts = np.full(n, 16, np.int64)
-    noisy = np.zeros(n, bool)
-    if pattern == "all":
-        counts[:] = 2
-    elif pattern == "alternating":
-        noisy[::2] = True
-    elif pattern == "single-last":
-        noisy[-1] = True
-    elif pattern == "below-min":
-        counts = rng.integers(0, 8, n)
-    elif pattern == "at-max":
-        noisy[:] = True
-        counts = rng.choice([31, 32, 40], n)
-    elif pattern == "random":
-        noisy = rng.random(n) < 0.5
-        counts = rng.integers(0, 40, n)
-    c = counts.astype(np.float64)
-    accum = np.stack([0.1 * c, 0.2 * c, 0.3 * c], 1) * (1 + rng.random((n, 1)))
-    S = (accum[:, 0] + accum[:, 1]) + accum[:, 2]
-    mean = S / np.maximum(c, 1)
-    m2 = S * mean * np.where(noisy, 2.0 + rng.random(n) * 5, 1.0)
-    if pattern == "v-negative":
-        m2 = S * mean * (1 - 1e-12)  # v = m2 - S * mean < 0: clamped to 0
-    if pattern == "nan-m2":
-        m2[::3] = np.nan
-        counts[::5] = MAX_C  # a NaN error samples on until max_count, not beyond
-    if pattern == "random":
-        m2[rng.random(n) < 0.1] = np.nan
-        accum[rng.random(n) < 0.1] = 0.0  # mean 0: the floor divides
-    return accum, m2, counts
-
-
-def select_numpy(accum, m2, counts, min_c=MIN_C, max_c=MAX_C, tol=TOL, floor=FLOOR):
-    with np.errstate(all="ignore"):
-        n = counts.astype(np.float64)
-        S = (accum[:, 0] + accum[:, 1]) + accum[:, 2]
-        mean = S / n
-        v = m2 - S * mean
-        v = np.where(v < 0, 0.0, v)
-        sem = np.sqrt((v / (n - 1)) / n)
-        err = sem / np.where(mean > floor, mean, floor)
-        err = np.where(counts < 2, 0.0, err)
-        sel = (counts < min_c) | ((counts < max_c) & ~(err <= tol))
-    return np.flatnonzero(sel), err
-
-
 @pytest.fixture(scope="module")
-def select_renderer():
-    r = rtzig.DeviceRenderer(0)
-    yield r
-    r.close()
+def select_renderer(module_renderers):
+    return module_renderers()
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, NPIX, 3 * SEL_BLOCK + 17])
@@ -422,13 +288,13 @@ def test_render_adaptive_end_to_end(oracle):
 
 
 # ---- the list walk, arguments ----------------------------------------------------------------------
-def test_chapter13_list_walk(oracle):
+def test_chapter13_list_walk(oracle, renderers):
     """5 spheres: the reference's list walk, geometry in LDS (the gather twin of lds_u4)."""
     def cam13(spp):
         return rtzig.chapter13_camera(width=W, aspect_ratio=16 / 9, spp=spp)
     cam = cam13(1)
     assert cam.width * cam.height == NPIX
-    r = renderer(cam)
+    r = renderers(cam)
     b = Bufs()
     A = list_a()
     b.add(r, cam, None, 5)
@@ -444,9 +310,9 @@ def test_chapter13_list_walk(oracle):
     assert int(b.stats[1]) == NPIX * 5 + len(A) * 4
 
 
-def test_arguments():
+def test_arguments(renderers):
     cam = cam37()
-    r = renderer(cam)
+    r = renderers(cam)
     b = Bufs(fill=7.0)
     before = b.bits()
     b.add(r, cam, None, 0)                      # no samples: OK, nothing touched

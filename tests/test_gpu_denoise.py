@@ -12,10 +12,11 @@ import torch
 import denoise_ref
 import domain_values
 import rtzig
+from gpu_support import DEV, rmse, same_bits
+from gpu_support import module_renderers, renderers  # noqa: F401 (fixtures)
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SHAPES = [(1, 1), (5, 3), (1, 40), (37, 23), (70, 45)]  # (W, H)
 LEVELS = [0, 1, 3, 6]                                   # at 6 the step of 32 exceeds several dimensions
 FORMS = [None, "tile", "direct"]                        # RTZIG_DENOISE_FORM: the default choice and both forced
@@ -112,16 +113,9 @@ class Device:
         return all(torch.equal(self.t[k].view(torch.uint8), self.before[k].view(torch.uint8)) for k in self.t)
 
 
-def same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.int64),
-                                                 np.ascontiguousarray(b).view(np.int64))
-
-
 @pytest.fixture(scope="module")
-def rend():
-    r = rtzig.DeviceRenderer(0)
-    yield r
-    r.close()
+def rend(module_renderers):
+    return module_renderers()
 
 
 # ---- the filter against its definition --------------------------------------------------------------
@@ -281,8 +275,8 @@ def test_other_stream_and_timing(rend):
     assert same_bits(out.cpu().numpy(), want_c) and same_bits(var.cpu().numpy(), want_v)
 
 
-def test_workspace_is_128_bytes_per_pixel_and_given_back():
-    r = rtzig.DeviceRenderer(0)
+def test_workspace_is_128_bytes_per_pixel_and_given_back(renderers):
+    r = renderers()
     base = r.workspace_bytes()
     for (W, H), want in (((70, 45), 128 * 3150),    # a fresh context: exactly the planes
                          ((64, 45), 128 * 3150),    # 2880 pixels: within 25% of what is held, kept
@@ -300,14 +294,13 @@ def test_workspace_is_128_bytes_per_pixel_and_given_back():
     r.close()
 
 
-def test_argument_errors_with_a_live_context_and_a_pending_deferred_pass(monkeypatch):
+def test_argument_errors_with_a_live_context_and_a_pending_deferred_pass(monkeypatch, renderers):
     """Every refusal leaves the buffers alone; a good call is a plain call: it first runs the reduce pass
     a deferred render left pending, whose frame is then complete on that render's out stream."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", "direct")
     cam = rtzig.final_scene_camera(width=37, aspect_ratio=16 / 9, spp=4)
     W, H = cam.width, cam.height
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam)
     plain = torch.zeros((H, W, 3), dtype=torch.float64, device=DEV)
     r.render_rows_async(cam.cam, plain.data_ptr())
     d = Device(W, H, synthetic("smooth", W, H))
@@ -370,13 +363,12 @@ def one_pass(spp):
     return _ONE_PASS[spp]
 
 
-def fill_buffers(cam, counts):
+def fill_buffers(make, cam, counts):
     """The buffers the test fills itself: every pixel brought to its count by gather passes (one pass per
     distinct count, over the pixels that have it), and FSPP feature samples.  Host arrays."""
     W, H = cam.width, cam.height
     P = W * H
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = make(cam)
     accum = torch.empty((P, 3), dtype=torch.float64, device=DEV)
     m2 = torch.empty(P, dtype=torch.float64, device=DEV)
     cnt = torch.zeros(P, dtype=torch.int32, device=DEV)
@@ -398,11 +390,7 @@ def fill_buffers(cam, counts):
     return host
 
 
-def rmse(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - b) ** 2)))
-
-
-def test_render_denoised_end_to_end(oracle):
+def test_render_denoised_end_to_end(oracle, renderers):
     cam = cam13()
     W, H = cam.width, cam.height
     res = rtzig.render_denoised(cam.cam, cam.scene.world, SPP, feature_spp=FSPP)
@@ -410,7 +398,7 @@ def test_render_denoised_end_to_end(oracle):
     assert res["variance"].shape == (H, W) and res["counts"].shape == (H, W) and res["counts"].dtype == np.uint32
     assert (res["counts"] == SPP).all()
     assert same_bits(res["noisy"], one_pass(SPP))
-    host = fill_buffers(cam, res["counts"])
+    host = fill_buffers(renderers, cam, res["counts"])
     want_c, want_v = denoise_ref.denoise(W, H, host["accum"], host["m2"], host["counts"], host["albedo"],
                                          host["normal"], host["depth"], host["hits"], FSPP)
     assert same_bits(res["image"], want_c) and same_bits(res["variance"], want_v)  # the layers add nothing
@@ -426,7 +414,7 @@ def test_render_denoised_end_to_end(oracle):
     assert same_bits(res8["variance"], res["variance"])
 
 
-def test_render_denoised_adaptive():
+def test_render_denoised_adaptive(renderers):
     cam = cam13()
     W, H = cam.width, cam.height
     res = rtzig.render_denoised(cam.cam, cam.scene.world, SPP, feature_spp=FSPP,
@@ -439,7 +427,7 @@ def test_render_denoised_adaptive():
     assert same_bits(res["noisy"], want_noisy)
     img, cnt = rtzig.render_adaptive(cam.cam, cam.scene.world, SPP, 64, 16, 0.05)
     assert np.array_equal(cnt, res["counts"]) and same_bits(img, res["noisy"])  # render_adaptive's loop, unchanged
-    host = fill_buffers(cam, counts)
+    host = fill_buffers(renderers, cam, counts)
     want_c, want_v = denoise_ref.denoise(W, H, host["accum"], host["m2"], host["counts"], host["albedo"],
                                          host["normal"], host["depth"], host["hits"], FSPP, levels=3)
     assert same_bits(res["image"], want_c) and same_bits(res["variance"], want_v)

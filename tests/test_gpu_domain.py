@@ -5,7 +5,7 @@ accumulator values no render produces.
 
 Every comparison is of bits (np.array_equal, or int64 views), and ray counts are equal.  The
 references never come from the code under test: oracle B (oracle_render_b / oracle_accumulate_b), the
-per-sample Python reference of tests/test_gpu_features.py, numpy, oracle.to_rgb8, or a count identity
+per-sample Python reference of tests/gpu_support.py, numpy, oracle.to_rgb8, or a count identity
 (a ray per sample when nothing can be hit)."""
 import math
 
@@ -16,14 +16,14 @@ import torch
 import domain_values as dv
 import fast_scenes
 import rtzig
+from fast_scenes import always_list_scene, far_origin_scene
+from gpu_support import (DEV, FLOOR, MAX_C, MIN_C, SEL_BLOCK, TOL, Buffers, add_sample, assert_equal, i32, list_a,
+                         select_numpy, synthetic)
+from gpu_support import module_renderers, renderers  # noqa: F401 (fixtures)
 from rtzig.abi import D3, RT_LAMBERTIAN, RtCamera, RtSphere
-from test_gpu_adaptive import FLOOR, MAX_C, MIN_C, SEL_BLOCK, TOL, list_a, select_numpy, synthetic
-from test_gpu_features import Buffers, add_sample, assert_equal
-from test_gpu_parity import always_list_scene, far_origin_scene
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 INF = math.inf
 MODES = ["ring", "direct"]
 # t_min is 1e-3 everywhere here: -1, 0, 1e-3 and -inf leave an empty interval; 1e300 is inf as f32
@@ -100,13 +100,6 @@ def sky_only(oracle, name):
     return _REFS[key]
 
 
-def renderer(cam, precision="f64"):
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
-    r.set_precision(precision)
-    return r
-
-
 def render_rows(r, c):
     """One render of camera struct c on renderer r: (image, rays, samples)."""
     out = torch.full((c.image_height, c.image_width, 3), float("nan"), dtype=torch.float64, device=DEV)
@@ -121,11 +114,6 @@ def fill(n, width=3, salt=0):
     """A known finite pattern for a pre-filled accumulator: dyadic values in [0.25, 16)."""
     a = ((np.arange(n * width, dtype=np.int64) * 7919 + salt) % 1009) / 64.0 + 0.25
     return a.reshape(n, width) if width > 1 else a
-
-
-def i32(x):
-    """The int32 with the bits of the uint32 x (torch has no uint32 arithmetic; the device reads u32)."""
-    return int(np.array(x, np.uint32).view(np.int32))
 
 
 # ---- finite t_max ------------------------------------------------------------------------------------
@@ -156,12 +144,12 @@ def test_tmax_changes_the_image_on_the_oracle(oracle):
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("variant", ["bvh", "smem_u4", "lds_u4"])
-def test_tmax_final_scene_every_walk(oracle, variant, mode, monkeypatch):
+def test_tmax_final_scene_every_walk(oracle, variant, mode, monkeypatch, renderers):
     """The BVH walk and both list walks, in both unit modes (separate instantiations): `closest`
     starts from t_max in each."""
     monkeypatch.setenv("RTZIG_KERNEL", variant)
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
-    r = renderer(scene("final64"))
+    r = renderers(scene("final64"))
     for t_max in TMAX:
         check_tmax(oracle, "final64", r, t_max, (variant, mode, t_max))
         name = r.kernel_name()
@@ -171,9 +159,9 @@ def test_tmax_final_scene_every_walk(oracle, variant, mode, monkeypatch):
     r.close()
 
 
-def test_tmax_trained_tree(oracle, monkeypatch):
+def test_tmax_trained_tree(oracle, monkeypatch, renderers):
     monkeypatch.setenv("RTZIG_BVH_TRAIN", "1")
-    r = renderer(scene("final64"))
+    r = renderers(scene("final64"))
     for t_max in TMAX:
         check_tmax(oracle, "final64", r, t_max, ("trained", t_max))
         assert r.tree_info()["trained"] == 1
@@ -181,7 +169,7 @@ def test_tmax_trained_tree(oracle, monkeypatch):
 
 
 @pytest.mark.parametrize("name", ["large", "always", "far", "materials64"])
-def test_tmax_other_structures(oracle, name, monkeypatch):
+def test_tmax_other_structures(oracle, name, monkeypatch, renderers):
     """The global-memory tree (2600 spheres), the always-list's runtime loop (more than four entries),
     the far-origin walk without culling (RTZIG_BVH_ORIGIN_SCALE shrinks the bound so that ordinary
     rays take it) and the materials scene (7 spheres: the list walk from LDS)."""
@@ -189,7 +177,7 @@ def test_tmax_other_structures(oracle, name, monkeypatch):
         monkeypatch.setenv("RTZIG_KERNEL", "bvh")
     if name == "far":
         monkeypatch.setenv("RTZIG_BVH_ORIGIN_SCALE", "0.05")
-    r = renderer(scene(name))
+    r = renderers(scene(name))
     info = r.tree_info()
     for t_max in TMAX:
         check_tmax(oracle, name, r, t_max, (name, t_max))
@@ -206,7 +194,7 @@ def test_tmax_other_structures(oracle, name, monkeypatch):
 
 
 def feature_sums(oracle, c, spheres, begin, count, start=None):
-    """The per-sample Python reference of tests/test_gpu_features.py over samples [begin, begin + count),
+    """The per-sample Python reference of tests/gpu_support.py over samples [begin, begin + count),
     added onto `start` (four arrays; None: zeros)."""
     P = c.image_width * c.image_height
     if start is None:
@@ -223,13 +211,13 @@ def feature_sums(oracle, c, spheres, begin, count, start=None):
     ("chapter13", "lds_u4(features)", None, [1.2, 1e-3]),
     ("large", "bvh_global(features)", None, [1.2, -1.0]),
 ], ids=["bvh_lds", "smem_u4", "lds_u4", "bvh_global"])
-def test_tmax_feature_pass(oracle, name, kernel, env, values, monkeypatch):
+def test_tmax_feature_pass(oracle, name, kernel, env, values, monkeypatch, renderers):
     """The feature pass's closest hit lies in (t_min, t_max) too; an empty interval leaves hits 0."""
     if env:
         monkeypatch.setenv("RTZIG_KERNEL", env)
     cam = scene(name)
     n = 2 if name == "large" else 3
-    r = renderer(cam)
+    r = renderers(cam)
     P = cam.width * cam.height
     unbounded = None
     for t_max in [INF] + list(values):
@@ -294,9 +282,9 @@ def gather_case(oracle, r, cam, c, base, n, where):
     return want_acc
 
 
-def test_tmax_gather_pass(oracle):
+def test_tmax_gather_pass(oracle, renderers):
     cam = scene("final37")
-    r = renderer(cam)
+    r = renderers(cam)
     sky = None
     for t_max in TMAX:
         c = with_fields(cam.cam, t_max=t_max)
@@ -317,10 +305,10 @@ def test_seed_bit_63_changes_the_image_on_the_oracle(oracle):
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_seeds_colour_render(oracle, mode, monkeypatch):
+def test_seeds_colour_render(oracle, mode, monkeypatch, renderers):
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = scene("final64")
-    r = renderer(cam)
+    r = renderers(cam)
     for seed in SEEDS:
         img, rays, samples = render_rows(r, with_fields(cam.cam, seed=seed))
         ref, ref_rays = ref_b(oracle, "final64", seed=seed)
@@ -329,9 +317,9 @@ def test_seeds_colour_render(oracle, mode, monkeypatch):
     r.close()
 
 
-def test_seeds_feature_pass(oracle):
+def test_seeds_feature_pass(oracle, renderers):
     cam = scene("final37")
-    r = renderer(cam)
+    r = renderers(cam)
     for seed in SEEDS:
         c = with_fields(cam.cam, seed=seed)
         buf = Buffers(740, poison=True)
@@ -341,9 +329,9 @@ def test_seeds_feature_pass(oracle):
     r.close()
 
 
-def test_seeds_gather_pass(oracle):
+def test_seeds_gather_pass(oracle, renderers):
     cam = scene("final37")
-    r = renderer(cam)
+    r = renderers(cam)
     for seed in SEEDS:
         gather_case(oracle, r, cam, with_fields(cam.cam, seed=seed), 0, 3, hex(seed))
     r.close()
@@ -355,12 +343,12 @@ RANGES = [(2 ** 31 - 7, 20), (LAST - 100, 100)]  # across 2^31; the last 100 sam
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("begin, count", RANGES, ids=["across-2^31", "last-100"])
-def test_high_sample_range_onto_a_filled_accumulator(oracle, begin, count, mode, monkeypatch):
+def test_high_sample_range_onto_a_filled_accumulator(oracle, begin, count, mode, monkeypatch, renderers):
     """Ring mode's chunk table (s_begin + rel[i]) and direct mode's sample number (fs + s_begin) with
     bit 31 set, continued from stored sums; a two-call split of the range gives the same bits."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = scene("final37")
-    r = renderer(cam)
+    r = renderers(cam)
     acc0 = fill(740)
     want, want_rays = oracle.accumulate_b(cam.cam, cam.scene.world, begin, count, acc0.reshape(20, 37, 3), threads=16)
     for split in ([count], [37, count - 37] if count > 37 else [7, count - 7]):
@@ -380,19 +368,19 @@ def test_high_sample_range_onto_a_filled_accumulator(oracle, begin, count, mode,
 
 
 @pytest.mark.parametrize("base, n", [(2 ** 31 - 7, 12), (LAST - 12, 12)], ids=["across-2^31", "to-the-last-count"])
-def test_high_counts_gather_pass(oracle, base, n):
+def test_high_counts_gather_pass(oracle, base, n, renderers):
     """The gather pass builds the sample number as counts[p] + k, in the seed window and per lane."""
     cam = scene("final37")
-    r = renderer(cam)
+    r = renderers(cam)
     gather_case(oracle, r, cam, cam.cam, base, n, (base, n))
     r.close()
 
 
-def test_high_sample_begin_feature_pass(oracle):
+def test_high_sample_begin_feature_pass(oracle, renderers):
     cam = scene("final37")
     begin = LAST - 8
     start = (fill(740), fill(740, salt=3), fill(740, 1, salt=7), np.full(740, 3, np.uint32))
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(740)
     for t, a in zip((buf.albedo, buf.normal, buf.depth), start):
         t.copy_(torch.from_numpy(a))
@@ -410,10 +398,8 @@ def test_high_sample_begin_feature_pass(oracle):
 
 # ---- selection beyond one scan round, and counts above 2^31 ------------------------------------------
 @pytest.fixture(scope="module")
-def ctx():
-    r = rtzig.DeviceRenderer(0)
-    yield r
-    r.close()
+def ctx(module_renderers):
+    return module_renderers()
 
 
 def run_select(r, accum, m2, counts, min_c, max_c, tol, floor):

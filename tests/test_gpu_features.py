@@ -2,84 +2,23 @@
 unscaled sums over samples [0, n) of the camera ray's first-hit albedo, shading normal and Euclidean
 depth, and the number of samples that hit.
 
-The reference is computed here, on the CPU, from the oracle's helpers alone: per (pixel, sample) the
+The reference (tests/gpu_support.py) is computed on the CPU from the oracle's helpers alone: per (pixel, sample) the
 draws of the stream oracle.sample_key(seed, pixel, sample), getRay restated in Python floats (IEEE
 f64, no fused multiply-add, the operation order of oracle/rt_oracle.c get_ray / random_in_unit_disk),
 oracle.world_hit for the winning sphere and its root, oracle.sphere_hit for the normal, the albedo
 from the sphere, the depth as rt.h states it, all added in sample order from 0.0.  Every comparison is
 np.array_equal on the raw sums."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
 import fast_scenes
 import rtzig
-from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RtCamera, RtSphere
+from gpu_support import DEV, Buffers, assert_equal, cached, reference
+from gpu_support import renderers  # noqa: F401 (fixture)
+from rtzig.abi import D3, RT_LAMBERTIAN, RtCamera, RtSphere
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-MAX_DRAWS = 64  # 2 sampleSquare draws + 31 rejection trips: more is a test bug (p < 1e-20)
-
-
-# ---- the reference -----------------------------------------------------------------------------------
-def get_ray(cam, i, j, u):
-    """getRay (camera.zig:187-215) from the draws u of one sample's stream: (origin, direction)."""
-    ox = u[0] - 0.5
-    oy = u[1] - 0.5
-    fi, fj = float(i) + ox, float(j) + oy
-    ps = [(cam.pixel0[c] + cam.du[c] * fi) + cam.dv[c] * fj for c in range(3)]
-    if cam.defocus_angle <= 0:
-        origin = [cam.center[c] for c in range(3)]
-    else:
-        k = 2
-        while True:
-            assert k + 2 <= MAX_DRAWS, "more than 31 rejection trips: a test bug"
-            x = -1.0 + 2.0 * u[k]      # rdr(-1, 1) = -1 + (1 - -1) * u
-            y = -1.0 + 2.0 * u[k + 1]
-            k += 2
-            if x * x + y * y < 1:
-                break
-        origin = [(cam.center[c] + cam.defocus_disk_u[c] * x) + cam.defocus_disk_v[c] * y for c in range(3)]
-    return origin, [ps[c] - origin[c] for c in range(3)]
-
-
-def add_sample(oracle, cam, spheres, s, alb, nrm, dep, hits):
-    """Adds sample s of every pixel, in place, to the four sums (albedo (H*W, 3), normal (H*W, 3),
-    depth (H*W), hits (H*W) u32)."""
-    W, H = cam.image_width, cam.image_height
-    for p in range(H * W):
-        j, i = divmod(p, W)
-        u = [float(x) for x in oracle.random_doubles(oracle.sample_key(cam.seed, p, s), MAX_DRAWS)]
-        orig, d = get_ray(cam, i, j, u)
-        k, t = oracle.world_hit(spheres, orig, d, cam.t_min, cam.t_max)
-        if k < 0:
-            continue  # a miss contributes exactly nothing
-        sp = spheres[k]
-        rec = oracle.sphere_hit(sp, orig, d, cam.t_min, cam.t_max)
-        assert rec is not None and rec["t"] == t
-        a = (1.0, 1.0, 1.0) if sp.material == RT_DIELECTRIC else tuple(sp.albedo)
-        depth = t * math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
-        for c in range(3):
-            alb[p, c] = alb[p, c] + a[c]
-            nrm[p, c] = nrm[p, c] + rec["normal"][c]
-        dep[p] = dep[p] + depth
-        hits[p] += 1
-
-
-def reference(oracle, cam, spheres, n_samples):
-    """Prefix sums: ref[n] = (albedo (H*W, 3), normal (H*W, 3), depth (H*W), hits (H*W) u32) after
-    samples [0, n), for n = 0..n_samples."""
-    W, H = cam.image_width, cam.image_height
-    alb, nrm = np.zeros((H * W, 3)), np.zeros((H * W, 3))
-    dep, hits = np.zeros(H * W), np.zeros(H * W, np.uint32)
-    ref = [(alb.copy(), nrm.copy(), dep.copy(), hits.copy())]
-    for s in range(n_samples):
-        add_sample(oracle, cam, spheres, s, alb, nrm, dep, hits)
-        ref.append((alb.copy(), nrm.copy(), dep.copy(), hits.copy()))
-    return ref
 
 
 def materials48():
@@ -102,56 +41,19 @@ SCENES = {
     "straddle48": (straddle48, 2),
     "large": (fast_scenes.large, 2),
 }
-_CACHE = {}
 
 
 def scene_ref(oracle, name):
     """(camera, reference prefix sums) of a scene, computed once and left unchanged."""
-    if name not in _CACHE:
-        make, n = SCENES[name]
-        cam = make()
+    def make():
+        factory, n = SCENES[name]
+        cam = factory()
         ref = reference(oracle, cam.cam, cam.scene.world, n)
         for arrs in ref:
             for a in arrs:
                 a.setflags(write=False)
-        _CACHE[name] = (cam, ref)
-    return _CACHE[name]
-
-
-# ---- device helpers -----------------------------------------------------------------------------------
-def renderer(cam, precision="f64"):
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
-    r.set_precision(precision)
-    return r
-
-
-class Buffers:
-    """The four device buffers of P pixels, optionally pre-filled with NaN / 0xFFFFFFFF."""
-
-    def __init__(self, P, poison=False):
-        self.albedo = torch.empty((P, 3), dtype=torch.float64, device=DEV)
-        self.normal = torch.empty((P, 3), dtype=torch.float64, device=DEV)
-        self.depth = torch.empty(P, dtype=torch.float64, device=DEV)
-        self.hits = torch.empty(P, dtype=torch.int32, device=DEV)  # u32 on the device
-        if poison:
-            for t in (self.albedo, self.normal, self.depth):
-                t.fill_(float("nan"))
-            self.hits.fill_(-1)
-
-    def ptrs(self):
-        return dict(d_albedo_ptr=self.albedo.data_ptr(), d_normal_ptr=self.normal.data_ptr(),
-                    d_depth_ptr=self.depth.data_ptr(), d_hits_ptr=self.hits.data_ptr())
-
-    def host(self):
-        torch.cuda.synchronize()
-        return (self.albedo.cpu().numpy(), self.normal.cpu().numpy(), self.depth.cpu().numpy(),
-                self.hits.cpu().numpy().view(np.uint32))
-
-
-def assert_equal(got, want, what=""):
-    for name, g, w in zip(("albedo", "normal", "depth", "hits"), got, want):
-        assert g.dtype == w.dtype and np.array_equal(g, w), (what, name, int((g != w).sum()))
+        return cam, ref
+    return cached(("features", name), make)
 
 
 def run_split(r, cam, buf, split, ref=None, **rows):
@@ -166,10 +68,10 @@ def run_split(r, cam, buf, split, ref=None, **rows):
 
 # ---- the final scene: LDS tree, ground on the always-list, a partial last wave ------------------------
 @pytest.mark.parametrize("split", [[8], [1, 7], [3, 5], [2, 2, 2, 2]], ids=lambda s: "-".join(map(str, s)))
-def test_final_scene_every_prefix_of_every_split_equals_the_reference(oracle, split):
+def test_final_scene_every_prefix_of_every_split_equals_the_reference(oracle, split, renderers):
     cam, ref = scene_ref(oracle, "final37")
     assert (cam.height, cam.width) == (20, 37) and len(cam.scene.world) == 485
-    r = renderer(cam)
+    r = renderers(cam)
     info = r.tree_info()
     assert info["bvh"] == 1 and info["always"] >= 1
     buf = Buffers(740)
@@ -180,10 +82,10 @@ def test_final_scene_every_prefix_of_every_split_equals_the_reference(oracle, sp
     assert ref[8][3].max() == 8 and ref[8][3].min() == 0  # the image has both covered and open pixels
 
 
-def test_new_image_overwrites_poisoned_buffers(oracle):
+def test_new_image_overwrites_poisoned_buffers(oracle, renderers):
     """sample_begin = 0 neither reads nor keeps what the buffers held (NaN / 0xFFFFFFFF here)."""
     cam, ref = scene_ref(oracle, "final37")
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(740, poison=True)
     run_split(r, cam, buf, [3, 5])
     got = buf.host()
@@ -193,10 +95,10 @@ def test_new_image_overwrites_poisoned_buffers(oracle):
 
 
 # ---- the other closest-hit structures and edge cases ---------------------------------------------------
-def test_chapter13_list_walk_nested_dielectric(oracle):
+def test_chapter13_list_walk_nested_dielectric(oracle, renderers):
     cam, ref = scene_ref(oracle, "chapter13")
     assert len(cam.scene.world) == 5
-    r = renderer(cam)
+    r = renderers(cam)
     assert r.tree_info()["bvh"] == 0
     buf = Buffers(cam.width * cam.height)
     run_split(r, cam, buf, [8], ref)
@@ -205,7 +107,7 @@ def test_chapter13_list_walk_nested_dielectric(oracle):
     r.close()
 
 
-def test_materials_duplicate_sphere_zero_radius_defocus(oracle):
+def test_materials_duplicate_sphere_zero_radius_defocus(oracle, renderers):
     """The exact duplicate (spheres 4 and 5) must give the lower index's albedo; the scene also holds a
     zero-radius sphere and a defocus disk."""
     cam, ref = scene_ref(oracle, "materials48")
@@ -213,24 +115,24 @@ def test_materials_duplicate_sphere_zero_radius_defocus(oracle):
     assert (cam.width, cam.cam.defocus_angle) == (48, 2.0)
     assert list(w[4].center) == list(w[5].center) and w[4].radius == w[5].radius and w[6].radius == 0.0
     assert tuple(w[4].albedo) != tuple(w[5].albedo)
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(cam.width * cam.height)
     run_split(r, cam, buf, [1, 3], ref)
     r.sync()
     r.close()
 
 
-def test_straddle_huge_far_spheres_on_the_always_list(oracle, monkeypatch):
+def test_straddle_huge_far_spheres_on_the_always_list(oracle, monkeypatch, renderers):
     """Five spheres walk the list by default; RTZIG_KERNEL=bvh walks the tree, whose always-list holds
     the two huge far spheres.  Both equal the reference."""
     cam, ref = scene_ref(oracle, "straddle48")
     assert cam.cam.defocus_angle == 0.0
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(cam.width * cam.height)
     run_split(r, cam, buf, [2], ref)
     r.close()
     monkeypatch.setenv("RTZIG_KERNEL", "bvh")
-    r = renderer(cam)
+    r = renderers(cam)
     info = r.tree_info()
     assert info["bvh"] == 1 and info["always"] >= 2
     buf = Buffers(cam.width * cam.height, poison=True)
@@ -241,10 +143,10 @@ def test_straddle_huge_far_spheres_on_the_always_list(oracle, monkeypatch):
     assert ref[2][3].max() > 0
 
 
-def test_large_scene_global_memory_tree(oracle):
+def test_large_scene_global_memory_tree(oracle, renderers):
     cam, ref = scene_ref(oracle, "large")
     assert len(cam.scene.world) == 2600 and (cam.width, cam.height) == (96, 54)
-    r = renderer(cam)
+    r = renderers(cam)
     assert r.tree_info()["bvh"] == 1
     buf = Buffers(96 * 54)
     run_split(r, cam, buf, [1, 1], ref)
@@ -255,10 +157,10 @@ def test_large_scene_global_memory_tree(oracle):
 
 # ---- partition independence ------------------------------------------------------------------------------
 @pytest.mark.parametrize("row0, row_step", [(1, 3), (0, 3), (19, 1)])
-def test_row_interleave_equals_the_matching_rows(oracle, row0, row_step):
+def test_row_interleave_equals_the_matching_rows(oracle, row0, row_step, renderers):
     cam, ref = scene_ref(oracle, "final37")
     rows = list(range(row0, 20, row_step))
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(len(rows) * 37)
     run_split(r, cam, buf, [5, 3], row0=row0, row_step=row_step)
     got = buf.host()
@@ -269,9 +171,9 @@ def test_row_interleave_equals_the_matching_rows(oracle, row0, row_step):
 
 
 @pytest.mark.parametrize("only", ["albedo", "normal", "depth", "hits"])
-def test_each_buffer_alone_equals_its_part_of_the_full_call(oracle, only):
+def test_each_buffer_alone_equals_its_part_of_the_full_call(oracle, only, renderers):
     cam, ref = scene_ref(oracle, "final37")
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(740, poison=True)
     keep = [t.clone() for t in (buf.albedo, buf.normal, buf.depth, buf.hits)]
     ptr = {k: v for k, v in buf.ptrs().items() if k == f"d_{only}_ptr"}
@@ -287,9 +189,9 @@ def test_each_buffer_alone_equals_its_part_of_the_full_call(oracle, only):
             assert np.array_equal(g.view(np.uint8), k.cpu().numpy().view(np.uint8)), name
 
 
-def test_all_null_buffers_and_empty_calls_touch_nothing(oracle):
+def test_all_null_buffers_and_empty_calls_touch_nothing(oracle, renderers):
     cam, _ = scene_ref(oracle, "final37")
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(740, poison=True)
     keep = [t.clone() for t in (buf.albedo, buf.normal, buf.depth, buf.hits)]
     name = r.kernel_name()
@@ -304,12 +206,12 @@ def test_all_null_buffers_and_empty_calls_touch_nothing(oracle):
         assert np.array_equal(t.cpu().numpy().view(np.uint8), k.cpu().numpy().view(np.uint8))
 
 
-def test_f32_context_gives_the_f64_contexts_bits(oracle):
+def test_f32_context_gives_the_f64_contexts_bits(oracle, renderers):
     """The pass is always parity arithmetic on the parity stream; on chapter 13 an F32 context also
     holds another structure (fast mode walks the tree of tiny scenes), which changes nothing."""
     for name, n in (("final37", 8), ("chapter13", 8)):
         cam, ref = scene_ref(oracle, name)
-        r = renderer(cam, precision="f32")
+        r = renderers(cam, precision="f32")
         assert r.tree_info()["bvh"] == 1
         buf = Buffers(cam.width * cam.height)
         run_split(r, cam, buf, [3, n - 3])
@@ -320,10 +222,10 @@ def test_f32_context_gives_the_f64_contexts_bits(oracle):
         assert_equal(got, ref[n], name)
 
 
-def test_forced_list_walk_on_the_final_scene(oracle, monkeypatch):
+def test_forced_list_walk_on_the_final_scene(oracle, monkeypatch, renderers):
     monkeypatch.setenv("RTZIG_KERNEL", "smem_u4")
     cam, ref = scene_ref(oracle, "final37")
-    r = renderer(cam)
+    r = renderers(cam)
     assert r.tree_info()["bvh"] == 0
     buf = Buffers(740)
     run_split(r, cam, buf, [8])
@@ -336,14 +238,14 @@ def test_forced_list_walk_on_the_final_scene(oracle, monkeypatch):
 
 @pytest.mark.parametrize("spread", [0, 2, 4])
 @pytest.mark.parametrize("name, kernel", [("final37", "bvh_lds"), ("chapter13", "lds_u4"), ("large", "bvh_global")])
-def test_every_lanes_per_pixel_form_gives_the_same_bits(oracle, monkeypatch, name, kernel, spread):
+def test_every_lanes_per_pixel_form_gives_the_same_bits(oracle, monkeypatch, name, kernel, spread, renderers):
     """1, 4 or 16 lanes per pixel (RTZIG_FEATURE_SPREAD forces the form a launch's size would pick):
     the additions are the same in the same order.  Passes of 3 and n - 3 samples: rounds with lanes
     past the pass's last sample, and more lanes than samples."""
     monkeypatch.setenv("RTZIG_FEATURE_SPREAD", str(spread))
     cam, ref = scene_ref(oracle, name)
     n = len(ref) - 1
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(cam.width * cam.height, poison=True)
     run_split(r, cam, buf, [n] if n < 4 else [3, n - 3], ref)
     assert r.kernel_name() == kernel + "(features)"
@@ -351,12 +253,12 @@ def test_every_lanes_per_pixel_form_gives_the_same_bits(oracle, monkeypatch, nam
     r.close()
 
 
-def test_trained_tree_gives_the_same_bits(oracle, monkeypatch):
+def test_trained_tree_gives_the_same_bits(oracle, monkeypatch, renderers):
     """A feature pass never trains; it walks the tree a colour pass left trained (RTZIG_BVH_TRAIN=1
     trains on this small launch)."""
     monkeypatch.setenv("RTZIG_BVH_TRAIN", "1")
     cam, ref = scene_ref(oracle, "final37")
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(740)
     run_split(r, cam, buf, [4])
     assert r.tree_info()["trained"] == 0  # the feature pass did not train
@@ -372,14 +274,14 @@ def test_trained_tree_gives_the_same_bits(oracle, monkeypatch):
 
 # ---- against the existing colour path ---------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["chapter13", "materials48"])
-def test_hits_agree_with_the_bounce_max_1_colour_render(oracle, name):
+def test_hits_agree_with_the_bounce_max_1_colour_render(oracle, name, renderers):
     """At bounce_max = 1 a sample that hits is black and a sample that misses is the (positive) sky:
     a pixel of the colour render is all-zero exactly where all n samples hit, and equals the render of
     a scene no ray hits (oracle B, same camera) exactly where none did.  Chapter 13 at 8 samples (its
     ground fills the view: every sample hits); the materials scene at 4 has all three kinds of pixel."""
     cam, ref = scene_ref(oracle, name)
     n = len(ref) - 1
-    r = renderer(cam)
+    r = renderers(cam)
     buf = Buffers(cam.width * cam.height)
     r.features(cam.cam, 0, n, d_hits_ptr=buf.hits.data_ptr())
     torch.cuda.synchronize()
@@ -404,9 +306,9 @@ def test_hits_agree_with_the_bounce_max_1_colour_render(oracle, name):
         assert (hits == n).any() and (hits == 0).any() and ((hits > 0) & (hits < n)).any()
 
 
-def test_colour_pass_between_feature_passes_changes_neither(oracle):
+def test_colour_pass_between_feature_passes_changes_neither(oracle, renderers):
     cam, ref = scene_ref(oracle, "final37")
-    r = renderer(cam)
+    r = renderers(cam)
     alone = torch.empty((740, 3), dtype=torch.float64, device=DEV)
     r.accumulate(cam.cam, alone.data_ptr(), 0, 6)
     buf = Buffers(740)

@@ -12,15 +12,15 @@ import pytest
 import torch
 
 import rtzig
+from gpu_support import renderers  # noqa: F401 (fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-def _partition_check(cam, n_parts=8):
+def _partition_check(make, cam, n_parts=8):
     H, W = cam.height, cam.width
     spp = cam.cam.samples_per_pixel
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = make(cam)
     full = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
     st = torch.zeros(2, dtype=torch.int64, device="cuda:0")
     r.render_rows_async(cam.cam, full.data_ptr(), d_stats_ptr=st.data_ptr())
@@ -36,18 +36,18 @@ def _partition_check(cam, n_parts=8):
     r.close()
 
 
-def test_config4_full_frame_partition_invariant():
+def test_config4_full_frame_partition_invariant(renderers):
     """Config 4, the bench workload: 1200x800, 500 spp, 485 spheres."""
-    _partition_check(rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=500))
+    _partition_check(renderers, rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=500))
 
 
-def test_config3_full_frame_partition_invariant():
+def test_config3_full_frame_partition_invariant(renderers):
     """Config 3: chapter 13 scene, 1200x675, 500 spp."""
-    _partition_check(rtzig.chapter13_camera(width=1200, spp=500))
+    _partition_check(renderers, rtzig.chapter13_camera(width=1200, spp=500))
 
 
-def test_config5_full_image_partition_invariant():
+def test_config5_full_image_partition_invariant(renderers):
     """Config 5's image, 3840x2160, at 200 of its 10000 spp (its full spp is one 9.7-s launch, run by
     tools/configs_bench.py; config 5's row at 10000 spp is checked against the oracle in
     test_gpu_configs.py)."""
-    _partition_check(rtzig.final_scene_camera(width=3840, aspect_ratio=16 / 9, spp=200))
+    _partition_check(renderers, rtzig.final_scene_camera(width=3840, aspect_ratio=16 / 9, spp=200))

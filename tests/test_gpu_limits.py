@@ -5,19 +5,19 @@ import pytest
 import torch
 
 import rtzig
+from gpu_support import renderers  # noqa: F401 (fixture)
 from rtzig.lib import RtError
 
 pytestmark = pytest.mark.gpu
 
 
-def test_too_many_units_is_refused():
+def test_too_many_units_is_refused(renderers):
     """16384 x 16384 pixels x 4 M spp: 4.2 M tiles x ~83 000 chunks (of up to kUnitS = 48 samples)
     > 2^32 units -> RT_ERR_CAPACITY, returned before any buffer is allocated or kernel launched (the
     context stays usable).  The output buffer is full-size, so a regression that launched anyway
     would run long, never write out of bounds."""
     big = rtzig.final_scene_camera(width=16384, aspect_ratio=1.0, spp=4_000_000)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(big.scene.world)
+    r = renderers(big.scene.world)
     full = torch.empty((big.height, big.width, 3), dtype=torch.float64, device="cuda:0")
     with pytest.raises(RtError) as e:
         r.render_rows_async(big.cam, full.data_ptr())
@@ -32,14 +32,13 @@ def test_too_many_units_is_refused():
 
 
 @pytest.mark.parametrize("mode", ["ring", "direct"])
-def test_8k_image_rows_bit_exact(oracle, mode, monkeypatch):
+def test_8k_image_rows_bit_exact(oracle, mode, monkeypatch, renderers):
     """An 8K frame (7680 x 4320, 2 spp: 66 M samples in one launch) equals oracle B on two crops of
     rows, and its rows equal the same rows rendered alone."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = rtzig.final_scene_camera(width=7680, aspect_ratio=16 / 9, spp=2)
     H, W = cam.height, cam.width
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     full = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
     r.render_rows_async(cam.cam, full.data_ptr())
     r.sync()
@@ -53,7 +52,7 @@ def test_8k_image_rows_bit_exact(oracle, mode, monkeypatch):
     r.close()
 
 
-def test_huge_scene_linear_walk_ring_mode(oracle, monkeypatch):
+def test_huge_scene_linear_walk_ring_mode(oracle, monkeypatch, renderers):
     """70 000 spheres: more than the BVH's depth bound holds (2^15 two-sphere leaves), so the tree
     does not build and the kernel walks the whole list (smem_u4) for every ray — ~100x the final
     scene's per-segment cost.  Ring mode forced with 2 tiles x 40 spp, so units of the same tile
@@ -80,8 +79,7 @@ def test_huge_scene_linear_walk_ring_mode(oracle, monkeypatch):
     cam = (rtzig.Camera.builder(16, 2.0).setScene(scene).setDefocusAngle(0.6).setFocusDist(10.0)
            .setViewport((13, 2, 3), (0, 0, 0), 20.0).setSamplesPerPixel(40).build())
     assert cam.width * cam.height == 128
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(arr)
+    r = renderers(arr)
     out = torch.zeros((cam.height, cam.width, 3), dtype=torch.float64, device="cuda:0")
     stats = torch.zeros(2, dtype=torch.int64, device="cuda:0")
     r.render_rows_async(cam.cam, out.data_ptr(), d_stats_ptr=stats.data_ptr())
@@ -93,7 +91,7 @@ def test_huge_scene_linear_walk_ring_mode(oracle, monkeypatch):
     assert int(stats[0]) == rays
 
 
-def test_stalled_handoff_reports_error_and_recovers(oracle, monkeypatch):
+def test_stalled_handoff_reports_error_and_recovers(oracle, monkeypatch, renderers):
     """The bounded hand-off wait's give-up path (rt_units.h).  With the bound shortened to 0 µs
     (test hook RTZIG_STALL_US) a wave that has to wait for a predecessor unit gives up on its second
     poll, sets the sticky error word and leaves; the launch must end (not hang) and report
@@ -107,8 +105,7 @@ def test_stalled_handoff_reports_error_and_recovers(oracle, monkeypatch):
            .setDefocusAngle(0.6).setFocusDist(10).setViewport((13, 2, 3), (0, 0, 0), 20)
            .setSamplesPerPixel(700).build())
     ref, _ = oracle.render_b(cam.cam, cam.scene.world)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     out = torch.zeros((1, 1, 3), dtype=torch.float64, device="cuda:0")
     monkeypatch.setenv("RTZIG_STALL_US", "0")
     r.render_rows_async(cam.cam, out.data_ptr())
@@ -130,7 +127,7 @@ def test_stalled_handoff_reports_error_and_recovers(oracle, monkeypatch):
     assert np.array_equal(rtzig.render(cam.cam, cam.scene.world, n_gpus=1), ref)
 
 
-def test_workspace_sized_to_the_launch(oracle):
+def test_workspace_sized_to_the_launch(oracle, renderers):
     """The context's workspace follows the kernel it launches (rt.h "Workspace"): config 4's whole
     frame (ring mode, the BVH kernel's 16 resident waves per CU) holds at most 0.6 GiB; a rank's rows
     of an 8-GPU job (direct mode) hold their stored samples and no ring; back in ring mode the
@@ -138,8 +135,7 @@ def test_workspace_sized_to_the_launch(oracle):
     both equals oracle B (reference: camera.zig:125 allocates only the W x H framebuffer)."""
     cam = rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=500)
     H, W = cam.height, cam.width
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     full = torch.zeros((H, W, 3), dtype=torch.float64, device="cuda:0")
     r.render_rows_async(cam.cam, full.data_ptr())
     r.sync()

@@ -5,23 +5,16 @@ image must equal the 1-rank GPU image and oracle B bit for bit: the RNG is keyed
 so the partition cannot change a bit.  (bench.py runs the same partition over RCCL, one GPU per
 rank.)"""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
+from ports import free_port
+
 pytestmark = pytest.mark.gpu
 
 WIDTH, SPP = 160, 6
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _rank(rank, world, port, q, mode):
@@ -63,7 +56,7 @@ def test_hip_ranks_gather_equals_single_rank(oracle, world, mode):
     import rtzig
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_rank, args=(r, world, port, q, mode)) for r in range(world)]
     for p in procs:
         p.start()

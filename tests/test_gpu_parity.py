@@ -13,8 +13,10 @@ import numpy as np
 import pytest
 
 import rtzig
+from fast_scenes import always_list_scene, far_origin_scene, golden_params
+from gpu_support import box_rmse
+from gpu_support import renderers  # noqa: F401 (fixture)
 from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtSphere
-from test_oracle import golden_params
 
 pytestmark = pytest.mark.gpu
 INF = math.inf
@@ -45,11 +47,6 @@ def test_final_scene_golden_config_bit_exact(oracle):
     assert st["rays"] == rays
 
 
-def _box_rmse(a, b):
-    box = lambda x: x[:224].reshape(28, 8, 50, 8, 3).astype(np.float64).mean(axis=(1, 3))
-    return float(np.sqrt(((box(a) - box(b)) ** 2).mean()))
-
-
 def _check_vs_chapter14(oracle, rgb, golden_dir):
     """SURVEY §8(c) ladder 3: GPU (per-sample streams) vs the reference's own chapter14.ppm
     (sequential stream), calibrated like configs 2/3: per-channel image-mean |delta| <= 1.0 (8-bit
@@ -60,9 +57,9 @@ def _check_vs_chapter14(oracle, rgb, golden_dir):
     _, _, gold = read_ppm(open(os.path.join(golden_dir, "chapter14.ppm"), "rb").read())
     spheres, _ = oracle.scene_final(0xDEADBEEF)
     b, _ = oracle.render_b(oracle.camera_build(golden_params()), spheres, threads=16)
-    floor = _box_rmse(gold, oracle.to_rgb8(b))
+    floor = box_rmse(gold, oracle.to_rgb8(b))
     assert np.abs(rgb.astype(np.float64).mean(axis=(0, 1)) - gold.astype(np.float64).mean(axis=(0, 1))).max() <= 1.0
-    assert _box_rmse(rgb, gold) <= 1.5 * floor, (_box_rmse(rgb, gold), floor)
+    assert box_rmse(rgb, gold) <= 1.5 * floor, (box_rmse(rgb, gold), floor)
 
 
 def test_final_scene_statistically_matches_reference_golden(oracle, golden_dir):
@@ -97,14 +94,13 @@ def test_rgb8_output_matches_to_rgb(oracle):
     assert np.array_equal(rgb, oracle.to_rgb8(ref))
 
 
-def test_row_partition_invariance():
+def test_row_partition_invariance(renderers):
     """Rows rendered in any interleaved partition are bit-identical to the full render."""
     import torch
     cam = rtzig.final_scene_camera(width=320, aspect_ratio=16 / 9, spp=4)
     full, _ = gpu_render(cam, cam.scene.world, n_gpus=1)
     H, W = cam.height, cam.width
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     for G in (2, 3, 8):
         for g in range(G):
             n_rows = (H - g + G - 1) // G
@@ -406,12 +402,11 @@ def test_bvh_far_camera_rebuild(oracle, monkeypatch):
     assert np.array_equal(out, ref)
 
 
-def test_config5_crop_bit_exact(oracle):
+def test_config5_crop_bit_exact(oracle, renderers):
     """Config 5 geometry (3840x2160, 16/9, final scene) on a crop of rows at reduced spp."""
     cam = rtzig.final_scene_camera(width=3840, aspect_ratio=16 / 9, spp=2)
     assert (cam.width, cam.height) == (3840, 2160)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     import torch
     rows = [0, 700, 1333, 2159]
     for j in rows:
@@ -465,13 +460,12 @@ def test_interval_min_variants_bit_exact(oracle, t_min):
     assert np.array_equal(out, ref) and st["rays"] == rays
 
 
-def test_kernel_times_total_accumulates():
+def test_kernel_times_total_accumulates(renderers):
     """rt_context_kernel_times_total sums the HIP-event times of every launch since timing was
     enabled (bench.py reads it once after its timed region); per-call times stay available."""
     import torch
     cam = rtzig.final_scene_camera(width=120, aspect_ratio=1.5, spp=4)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     out = torch.zeros((cam.height, cam.width, 3), dtype=torch.float64, device="cuda:0")
     r.enable_timing(True)
     per = []
@@ -487,7 +481,7 @@ def test_kernel_times_total_accumulates():
     r.close()
 
 
-def test_event_log_across_call_kinds(monkeypatch):
+def test_event_log_across_call_kinds(monkeypatch, renderers):
     """Every call kind reserves its slots of the one event log through the same code: a row render, a
     feature pass, a gather pass in 2 sub-passes, a denoise and a temporal accumulation on one timed
     context log 1 + 1 + 2 + 1 + 1 launches, kernel_times() after each call covers that call's own
@@ -513,10 +507,8 @@ def test_event_log_across_call_kinds(monkeypatch):
                     albedo=f64(P, 3), normal=f64(P, 3), depth=f64(P), hits=torch.zeros(P, dtype=torch.int32, device=dev))
 
     cur, prev = frame(), frame()
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(scene.world)
-    fill = rtzig.DeviceRenderer(0)  # the previous frame's buffers, from an untimed context
-    fill.set_scene(scene.world)
+    r = renderers(scene.world)
+    fill = renderers(scene.world)  # the previous frame's buffers, from an untimed context
     fill.features(cam.cam, 0, 2, prev["albedo"].data_ptr(), prev["normal"].data_ptr(), prev["depth"].data_ptr(),
                   prev["hits"].data_ptr())
     fill.accumulate_pixels(cam.cam, None, 4, prev["accum"].data_ptr(), prev["m2"].data_ptr(), prev["counts"].data_ptr())
@@ -559,8 +551,7 @@ def test_event_log_across_call_kinds(monkeypatch):
     r.sync()
     again = out.cpu().numpy().copy()
     r.close()
-    fresh = rtzig.DeviceRenderer(0)
-    fresh.set_scene(scene.world)
+    fresh = renderers(scene.world)
     ref = f64(H, W, 3)
     fresh.render_rows_async(cam.cam, ref.data_ptr())
     fresh.sync()
@@ -600,34 +591,6 @@ def test_running_sum_handoff_chains(oracle, width, spp, monkeypatch):
     assert np.array_equal(out, ref) and st["rays"] == rays
 
 
-def always_list_scene(n_big, ground, n_unbound):
-    """The scene and camera of test_always_list_sizes_bit_exact (64 x 42, 4 spp): a grid of small
-    spheres with n_big radius-1.2 spheres among them, an optional radius-1000 ground and n_unbound
-    spheres centred at 2e30."""
-    rng = np.random.default_rng(100 + 10 * n_big + n_unbound + (5 if ground else 0))
-    sph = []
-    for a in range(-4, 4):
-        for b in range(-4, 4):
-            sph.append(RtSphere(center=D3(a + 0.9 * rng.uniform(), 0.2, b + 0.9 * rng.uniform()), radius=0.2,
-                                material=int(rng.integers(0, 3)), albedo=D3(*rng.uniform(0, 1, 3)),
-                                fuzz=float(rng.uniform(0, 0.5)), refraction_index=1.5))
-    for k in range(n_big):
-        sph.append(RtSphere(center=D3(-3.0 + 2.0 * k, 1.2, 0.3 * k), radius=1.2, material=k % 3,
-                            albedo=D3(0.7, 0.6, 0.5), fuzz=0.0, refraction_index=1.5))
-    if ground:
-        sph.insert(int(rng.integers(0, len(sph))), RtSphere(center=D3(0, -1000, 0), radius=1000.0, material=0,
-                                                            albedo=D3(0.5, 0.5, 0.5)))
-    for k in range(n_unbound):
-        sph.insert(int(rng.integers(0, len(sph))), RtSphere(center=D3(2e30, 1.0 + k, 0), radius=1.0, material=0,
-                                                            albedo=D3(0.5, 0.5, 0.5)))
-    arr = (RtSphere * len(sph))(*sph)
-    scene = rtzig.Scene.init(7)
-    scene.world = arr
-    cam = (rtzig.Camera.builder(64, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10.0)
-           .setViewport((13, 2, 3), (0, 0, 0), 20.0).setSamplesPerPixel(4).build())
-    return arr, cam
-
-
 @pytest.mark.parametrize("n_big,ground,n_unbound", [(0, False, 0), (0, True, 0), (1, True, 0), (2, True, 0),
                                                     (3, True, 0), (4, True, 0), (3, True, 2)])
 def test_always_list_sizes_bit_exact(oracle, n_big, ground, n_unbound):
@@ -642,18 +605,6 @@ def test_always_list_sizes_bit_exact(oracle, n_big, ground, n_unbound):
     out, st = gpu_render(cam, arr, n_gpus=1)
     ref, rays = oracle.render_b(cam.cam, arr, threads=8)
     assert np.array_equal(out, ref) and st["rays"] == rays
-
-
-def far_origin_scene(width=96):
-    """The scene and camera of test_far_origin_lanes_walk_without_culling: the final scene of seed
-    0xfa7 plus an unboundable radius-2e30 metal sphere."""
-    scene = rtzig.Scene.init(0xfa7).generateWorld()
-    huge = RtSphere(center=D3(0, -2e30, 0), radius=2e30, material=RT_METAL, albedo=D3(0.7, 0.7, 0.7), fuzz=0.3)
-    arr = (RtSphere * (len(scene.world) + 1))(*scene.world, huge)
-    scene.world = arr
-    cam = (rtzig.Camera.builder(width, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10)
-           .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(4).build())
-    return arr, cam
 
 
 @pytest.mark.parametrize("scale", [None, "0.0", "0.05"])
@@ -687,15 +638,14 @@ def test_render_cache_scene_switch(oracle):
     assert np.array_equal(out, ra)
 
 
-def test_device_renderer_alternating_streams_and_cameras(oracle):
+def test_device_renderer_alternating_streams_and_cameras(oracle, renderers):
     """One context used from two HIP streams with different cameras: each call waits for the
     previous call's work before reusing the context's buffers (rt.h), so both images are exact."""
     import torch
     cam1 = rtzig.final_scene_camera(width=200, aspect_ratio=16 / 9, spp=9)
     cam2 = (rtzig.Camera.builder(200, 16 / 9).setScene(cam1.scene).setDefocusAngle(0.0).setFocusDist(4)
             .setViewport((-6, 3, 8), (0, 0.5, 0), 35).setSamplesPerPixel(7).build())
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam1.scene.world)
+    r = renderers(cam1.scene.world)
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     o1 = torch.zeros((cam1.height, 200, 3), dtype=torch.float64, device="cuda:0")
     o2 = torch.zeros((cam2.height, 200, 3), dtype=torch.float64, device="cuda:0")
@@ -710,7 +660,7 @@ def test_device_renderer_alternating_streams_and_cameras(oracle):
     r.close()
 
 
-def test_trained_tree_retrains_per_camera_across_streams(oracle, monkeypatch):
+def test_trained_tree_retrains_per_camera_across_streams(oracle, monkeypatch, renderers):
     """RTZIG_BVH_TRAIN=1: every camera switch rebuilds the tree from that camera's rays and
     re-uploads it while the previous render (on another stream) may still walk the old one; the
     context waits for it first (quiesce), so both cameras' images stay exact on every pass."""
@@ -719,8 +669,7 @@ def test_trained_tree_retrains_per_camera_across_streams(oracle, monkeypatch):
     cam1 = rtzig.final_scene_camera(width=160, aspect_ratio=16 / 9, spp=6)
     cam2 = (rtzig.Camera.builder(160, 16 / 9).setScene(cam1.scene).setDefocusAngle(0.3).setFocusDist(6)
             .setViewport((-5, 1.5, 9), (0, 0.3, 0), 30).setSamplesPerPixel(5).build())
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam1.scene.world)
+    r = renderers(cam1.scene.world)
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     o1 = torch.zeros((cam1.height, 160, 3), dtype=torch.float64, device="cuda:0")
     o2 = torch.zeros((cam2.height, 160, 3), dtype=torch.float64, device="cuda:0")
@@ -737,7 +686,7 @@ def test_trained_tree_retrains_per_camera_across_streams(oracle, monkeypatch):
 
 
 @pytest.mark.parametrize("profile", [False, True])
-def test_direct_rows_instrumented_bit_exact(oracle, profile, monkeypatch):
+def test_direct_rows_instrumented_bit_exact(oracle, profile, monkeypatch, renderers):
     """The launch shape of round 3's unexplained fault (profiles/r04_diag): direct-mode BVH rows of
     an 8-rank job, plain and with the instrumented kernel writing its 32-word stats.  Bit-exact
     against oracle B; exact sample and ray counts (reference: the row loop camera.zig:128-138 that a
@@ -745,9 +694,7 @@ def test_direct_rows_instrumented_bit_exact(oracle, profile, monkeypatch):
     import torch
     monkeypatch.setenv("RTZIG_UNIT_MODE", "direct")
     cam = rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=24)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
-    r.enable_profile(profile)
+    r = renderers(cam.scene.world, profile=profile)
     out = torch.zeros((12, 1200, 3), dtype=torch.float64, device="cuda:0")
     stats = torch.zeros(rtzig.abi.RT_PROFILE_STATS_WORDS, dtype=torch.int64, device="cuda:0")
     r.render_rows_async(cam.cam, out.data_ptr(), row0=3, row_step=8, n_rows=12, d_stats_ptr=stats.data_ptr())
@@ -761,7 +708,7 @@ def test_direct_rows_instrumented_bit_exact(oracle, profile, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", ["direct", "ring"])
-def test_split_render_pipeline_bit_exact(oracle, mode, monkeypatch):
+def test_split_render_pipeline_bit_exact(oracle, mode, monkeypatch, renderers):
     """rt_render_rows_async_split (bench.py's N > 1 frame pipeline): the sample kernel on one stream,
     the output completed on a second one (direct mode: the reduce pass there, over two per-sample
     buffers taken in turn).  Four frames back to back into two row buffers, each consumed on the
@@ -772,8 +719,7 @@ def test_split_render_pipeline_bit_exact(oracle, mode, monkeypatch):
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=24)
     ref, rays = oracle.render_b(cam.cam, cam.scene.world, row0=5, row_step=8, n_rows=12, threads=16)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     render, coll = torch.cuda.Stream(), torch.cuda.Stream()
     outs = [torch.zeros((12, 1200, 3), dtype=torch.float64, device="cuda:0") for _ in range(2)]
     stats = torch.zeros(2, dtype=torch.int64, device="cuda:0")
@@ -804,7 +750,7 @@ def test_split_render_pipeline_bit_exact(oracle, mode, monkeypatch):
 
 @pytest.mark.parametrize("mode", ["direct", "ring"])
 @pytest.mark.parametrize("profile", [False, True])
-def test_deferred_render_pipeline_bit_exact(oracle, mode, profile, monkeypatch):
+def test_deferred_render_pipeline_bit_exact(oracle, mode, profile, monkeypatch, renderers):
     """rt_render_rows_async_deferred: a direct-mode call's reduce pass is left pending and folded by
     the next deferred call's waves (one wave per block first, then the drained waves; the
     instrumented kernels do not fold, so a follow-up pass runs it after them: `profile`); the last
@@ -816,9 +762,7 @@ def test_deferred_render_pipeline_bit_exact(oracle, mode, profile, monkeypatch):
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=24)
     ref, rays = oracle.render_b(cam.cam, cam.scene.world, row0=5, row_step=8, n_rows=12, threads=16)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
-    r.enable_profile(profile)
+    r = renderers(cam.scene.world, profile=profile)
     render, coll = torch.cuda.Stream(), torch.cuda.Stream()
     outs = [torch.zeros((12, 1200, 3), dtype=torch.float64, device="cuda:0") for _ in range(2)]
     stats = torch.zeros(rtzig.abi.RT_PROFILE_STATS_WORDS, dtype=torch.int64, device="cuda:0")
@@ -862,7 +806,7 @@ def test_deferred_render_pipeline_bit_exact(oracle, mode, profile, monkeypatch):
     assert st[1] == 5 * 12 * 1200 * 24 and st[0] == 5 * rays
 
 
-def test_split_and_deferred_on_the_null_stream(oracle, monkeypatch):
+def test_split_and_deferred_on_the_null_stream(oracle, monkeypatch, renderers):
     """The output stream may be the HIP null stream (torch's default stream, handle 0 — the
     collective stream of bench.py): split and deferred calls then complete the output there, ordered
     after the sample kernel on the render stream.  Direct-mode rows, three frames each way, every
@@ -871,8 +815,7 @@ def test_split_and_deferred_on_the_null_stream(oracle, monkeypatch):
     monkeypatch.setenv("RTZIG_UNIT_MODE", "direct")
     cam = rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=24)
     ref, _ = oracle.render_b(cam.cam, cam.scene.world, row0=2, row_step=8, n_rows=12, threads=16)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     render, null = torch.cuda.Stream(), torch.cuda.default_stream()
     assert null.cuda_stream == 0
     outs = [torch.zeros((12, 1200, 3), dtype=torch.float64, device="cuda:0") for _ in range(3)]
@@ -896,7 +839,7 @@ def test_split_and_deferred_on_the_null_stream(oracle, monkeypatch):
         assert np.array_equal(img.cpu().numpy(), ref)
 
 
-def test_destroy_completes_pending_deferred_output(oracle, monkeypatch):
+def test_destroy_completes_pending_deferred_output(oracle, monkeypatch, renderers):
     """rt_context_destroy with a deferred call's reduce pass still pending runs the pass and waits
     for it before freeing the context: the output is complete and bit-exact against oracle B once
     destroy returns (the reference's render always fills ppm.pixels, camera.zig:125,138)."""
@@ -904,8 +847,7 @@ def test_destroy_completes_pending_deferred_output(oracle, monkeypatch):
     monkeypatch.setenv("RTZIG_UNIT_MODE", "direct")
     cam = rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=24)
     ref, rays = oracle.render_b(cam.cam, cam.scene.world, row0=3, row_step=8, n_rows=12, threads=16)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     render, coll = torch.cuda.Stream(), torch.cuda.Stream()
     out = torch.zeros((12, 1200, 3), dtype=torch.float64, device="cuda:0")
     stats = torch.zeros(2, dtype=torch.int64, device="cuda:0")
@@ -918,7 +860,7 @@ def test_destroy_completes_pending_deferred_output(oracle, monkeypatch):
     assert stats.cpu().tolist() == [rays, 12 * 1200 * 24]
 
 
-def test_deferred_alternating_out_streams(oracle, monkeypatch):
+def test_deferred_alternating_out_streams(oracle, monkeypatch, renderers):
     """Consecutive deferred calls on DIFFERENT out streams: the pending pass of call k is promised on
     call k's out stream, so call k+1 (another out stream) must not fold it on its own stream — it runs
     the pass whole on call k's stream first.  Each frame is read on its own out stream right after the
@@ -927,8 +869,7 @@ def test_deferred_alternating_out_streams(oracle, monkeypatch):
     monkeypatch.setenv("RTZIG_UNIT_MODE", "direct")
     cam = rtzig.final_scene_camera(width=1200, aspect_ratio=1.5, spp=24)
     ref, _ = oracle.render_b(cam.cam, cam.scene.world, row0=6, row_step=8, n_rows=12, threads=16)
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
+    r = renderers(cam.scene.world)
     render = torch.cuda.Stream()
     outs_s = [torch.cuda.Stream(), torch.cuda.Stream()]
     outs = [torch.zeros((12, 1200, 3), dtype=torch.float64, device="cuda:0") for _ in range(2)]

@@ -8,36 +8,13 @@ import pytest
 import torch
 
 import rtzig
+from gpu_support import DEV, cam37, ref37
+from gpu_support import renderers  # noqa: F401 (fixture)
 from rtzig.abi import RT_PROFILE_STATS_WORDS
 
 pytestmark = pytest.mark.gpu
 
 MODES = ["ring", "direct"]
-DEV = "cuda:0"
-
-
-def cam37(spp):
-    """37 x 20 = 740 pixels: a partial last tile (test_unit_schedule_sample_counts_bit_exact)."""
-    return rtzig.final_scene_camera(width=37, aspect_ratio=16 / 9, spp=spp)
-
-
-_REF37 = {}
-
-
-def ref37(oracle, n):
-    """Oracle B's image and rays of the 37-wide scene at spp = n (computed once per n)."""
-    if n not in _REF37:
-        cam = cam37(n)
-        _REF37[n] = oracle.render_b(cam.cam, cam.scene.world, threads=16)
-    return _REF37[n]
-
-
-def renderer(cam, precision="f64", profile=False):
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(cam.scene.world)
-    r.set_precision(precision)
-    r.enable_profile(profile)
-    return r
 
 
 def new_accum(n_pixels, fill=None):
@@ -64,7 +41,7 @@ def accumulate_all(r, cam, accum, split, stats=None, **rows):
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("split", [[100], [1, 99], [48, 52], [49, 1, 50], [17] * 5 + [15]], ids=lambda s: "-".join(map(str, s)))
-def test_every_prefix_equals_oracle_every_split_equals_one_pass(oracle, split, mode, monkeypatch):
+def test_every_prefix_equals_oracle_every_split_equals_one_pass(oracle, split, mode, monkeypatch, renderers):
     """Each pass's resolved image is oracle B at spp = samples_done; the last one is also the
     one-pass render at spp 100, its RGB8 resolve is Color.toRgb of it, and the passes' ray and
     sample counts sum to the one-pass counts."""
@@ -72,7 +49,7 @@ def test_every_prefix_equals_oracle_every_split_equals_one_pass(oracle, split, m
     cam = cam37(100)
     H, W = cam.height, cam.width
     assert (H, W) == (20, 37)
-    r = renderer(cam)
+    r = renderers(cam)
     accum = new_accum(H * W)
     stats = torch.zeros(2, dtype=torch.int64, device=DEV)
     done = 0
@@ -94,14 +71,14 @@ def test_every_prefix_equals_oracle_every_split_equals_one_pass(oracle, split, m
 
 
 @pytest.mark.parametrize("split", [[150, 150], [1, 299]], ids=lambda s: "-".join(map(str, s)))
-def test_seeded_sum_through_a_handoff_chain(oracle, split, monkeypatch):
+def test_seeded_sum_through_a_handoff_chain(oracle, split, monkeypatch, renderers):
     """One tile, many chunks per pass (test_running_sum_handoff_chains), ring mode forced: chunk 0 of
     the second pass takes the stored sum and every later chunk waits on the tile's flag."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", "ring")
     cam = (rtzig.Camera.builder(8, 1.0).setScene(rtzig.Scene.init(0x5eed).generateWorld())
            .setDefocusAngle(0.6).setFocusDist(10).setViewport((13, 2, 3), (0, 0, 0), 20)
            .setSamplesPerPixel(300).build())
-    r = renderer(cam)
+    r = renderers(cam)
     accum = new_accum(64)
     stats = torch.zeros(2, dtype=torch.int64, device=DEV)
     assert accumulate_all(r, cam, accum, split, stats) == 300
@@ -115,11 +92,11 @@ def test_seeded_sum_through_a_handoff_chain(oracle, split, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_new_image_overwrites_continuation_reads(oracle, mode, monkeypatch):
+def test_new_image_overwrites_continuation_reads(oracle, mode, monkeypatch, renderers):
     """sample_begin = 0 ignores what the accumulator held (NaN here; any sum would keep it)."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = cam37(100)
-    r = renderer(cam)
+    r = renderers(cam)
     accum = new_accum(740, fill=float("nan"))
     accumulate_all(r, cam, accum, [60, 40])
     img = resolved(r, accum, (20, 37), 100).cpu().numpy()
@@ -129,10 +106,10 @@ def test_new_image_overwrites_continuation_reads(oracle, mode, monkeypatch):
 
 
 @pytest.mark.parametrize("order", [("direct", "ring"), ("ring", "direct")], ids=lambda o: "-".join(o))
-def test_modes_may_change_between_passes(oracle, order, monkeypatch):
+def test_modes_may_change_between_passes(oracle, order, monkeypatch, renderers):
     """The accumulator is the same plain data in both modes: one pass in each on one buffer."""
     cam = cam37(100)
-    r = renderer(cam)
+    r = renderers(cam)
     accum = new_accum(740)
     done = 0
     for mode, count in zip(order, [48, 52]):
@@ -147,12 +124,12 @@ def test_modes_may_change_between_passes(oracle, order, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_row_subsets(oracle, mode, monkeypatch):
+def test_row_subsets(oracle, mode, monkeypatch, renderers):
     """Rows 1, 4, 7, ... into an accumulator of n_rows x W pixels."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = cam37(7)
     n_rows = len(range(1, 20, 3))
-    r = renderer(cam)
+    r = renderers(cam)
     accum = new_accum(n_rows * 37)
     accumulate_all(r, cam, accum, [3, 4], row0=1, row_step=3, n_rows=n_rows)
     img = resolved(r, accum, (n_rows, 37), 7).cpu().numpy()
@@ -163,12 +140,12 @@ def test_row_subsets(oracle, mode, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_no_host_sync_between_passes(oracle, mode, monkeypatch):
+def test_no_host_sync_between_passes(oracle, mode, monkeypatch, renderers):
     """Four passes and the resolve back to back on one non-default stream, one synchronize at the
     end: the accumulator is ordered across the launches by the stream alone."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = cam37(100)
-    r = renderer(cam)
+    r = renderers(cam)
     accum = new_accum(740)
     out = torch.empty((20, 37, 3), dtype=torch.float64, device=DEV)
     torch.cuda.synchronize()  # the allocations; nothing below waits on the host until the end
@@ -183,12 +160,12 @@ def test_no_host_sync_between_passes(oracle, mode, monkeypatch):
     assert np.array_equal(img, ref37(oracle, 100)[0])
 
 
-def test_after_a_pending_deferred_call(oracle, monkeypatch):
+def test_after_a_pending_deferred_call(oracle, monkeypatch, renderers):
     """An accumulate pass is a plain call: it first runs the reduce pass a deferred call left
     pending, whose output is then complete on that call's out stream."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", "direct")
     cam = cam37(100)
-    r = renderer(cam)
+    r = renderers(cam)
     frame = torch.zeros((20, 37, 3), dtype=torch.float64, device=DEV)
     accum = new_accum(740)
     torch.cuda.synchronize()
@@ -210,12 +187,12 @@ def test_after_a_pending_deferred_call(oracle, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_fast_mode(mode, monkeypatch):
+def test_fast_mode(mode, monkeypatch, renderers):
     """RT_PRECISION_F32: the passes resolve to the one-pass fast render's bits."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = rtzig.final_scene_camera(width=120, aspect_ratio=1.5, spp=16)
     H, W = cam.height, cam.width
-    r = renderer(cam, precision="f32")
+    r = renderers(cam, precision="f32")
     one = torch.zeros((H, W, 3), dtype=torch.float64, device=DEV)
     st1 = torch.zeros(2, dtype=torch.int64, device=DEV)
     r.render_rows_async(cam.cam, one.data_ptr(), d_stats_ptr=st1.data_ptr())
@@ -232,12 +209,12 @@ def test_fast_mode(mode, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", MODES)
-def test_instrumented_context(oracle, mode, monkeypatch):
+def test_instrumented_context(oracle, mode, monkeypatch, renderers):
     """The instrumented kernels (72-word stats) accumulate the same bits; words 0-1 of the passes
     sum to the one-pass counts."""
     monkeypatch.setenv("RTZIG_UNIT_MODE", mode)
     cam = cam37(7)
-    r = renderer(cam, profile=True)
+    r = renderers(cam, profile=True)
     accum = new_accum(740)
     stats = torch.zeros(RT_PROFILE_STATS_WORDS, dtype=torch.int64, device=DEV)
     accumulate_all(r, cam, accum, [3, 4], stats)
@@ -251,9 +228,9 @@ def test_instrumented_context(oracle, mode, monkeypatch):
     assert st[0] == rays and st[1] == 740 * 7
 
 
-def test_arguments():
+def test_arguments(renderers):
     cam = cam37(4)
-    r = renderer(cam)
+    r = renderers(cam)
     accum = new_accum(740, fill=7.0)
     torch.cuda.synchronize()
     r.accumulate(cam.cam, accum.data_ptr(), 5, 0)  # no samples: OK, nothing touched

@@ -11,11 +11,12 @@ import torch
 
 import rtzig
 import temporal_ref
+from gpu_support import DEV, bits, rmse, same_bits
+from gpu_support import module_renderers  # noqa: F401 (fixture)
 from rtzig.abi import RtCamera
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 SHAPES = [(1, 1), (5, 3), (1, 40), (37, 23), (70, 45)]  # (W, H)
 FS, FS_PREV = 4, 8                                      # feature samples of the two frames' guides
 R_WORLD = 12.0                                          # the synthetic world: the inside of this sphere
@@ -213,20 +214,9 @@ class Frames:
                    for k, v in self.t["cur"].items())
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.int64) if a.dtype == np.float64 else a
-
-
-def same(got, want):
-    return all(g.shape == w.shape and np.array_equal(bits(g), bits(w)) for g, w in zip(got, want))
-
-
 @pytest.fixture(scope="module")
-def rend():
-    r = rtzig.DeviceRenderer(0)
-    yield r
-    r.close()
+def rend(module_renderers):
+    return module_renderers()
 
 
 # ---- the kernel against its definition -----------------------------------------------------------------
@@ -242,7 +232,7 @@ def test_bits_against_numpy(rend, shape, pair):
                                                   min_weight=0.9)):
             want = fr.ref(**prm)
             got = fr.run(rend, rtzig.temporal_params(**prm))
-            assert same(got, want), (pattern, shape, pair, prm)
+            assert same_bits(got, want), (pattern, shape, pair, prm)
             taken += int((want[3] > 0).sum())
         assert fr.prev_unchanged()
     if pair in ("identical", "subpixel-pan"):
@@ -319,7 +309,7 @@ def test_exact_integer_coordinates_skip_the_zero_weight_taps(rend, shape):
     fr = Frames(cam, cur, prev_cam, prev)
     want = fr.ref(**wide)
     got = fr.run(rend, rtzig.temporal_params(**wide))
-    assert same(got, want)
+    assert same_bits(got, want)
     # independent of the reference: the taps are (i, j - 1) at weight 0.25 and (i, j) at 0.75, nothing else
     cnt = prev["counts"].reshape(H, W)
     up = np.vstack([np.full((1, W), 2 ** 40), cnt[:-1]])  # row -1 is outside the image
@@ -334,7 +324,7 @@ def test_null_guides(rend, skip):
     fr = Frames(cam, frame(cam, "random", "cur", FS), cam_prev, frame(cam_prev, "random", "prev", FS_PREV))
     prm = dict(sigma_z=1.0)  # the random depths pass: the guide tests decide
     want = fr.ref(skip=skip, **prm)
-    assert same(fr.run(rend, rtzig.temporal_params(**prm), skip=skip), want)
+    assert same_bits(fr.run(rend, rtzig.temporal_params(**prm), skip=skip), want)
     full = fr.ref(**prm)
     assert (want[3] > 0).sum() > (full[3] > 0).sum()  # the guide that left did refuse taps
     if len(skip) == 2:
@@ -361,9 +351,9 @@ def test_default_params_determinism_and_no_history_buffer(rend):
     want = fr.ref()
     a = fr.run(rend)  # params None: the defaults
     b = fr.run(rend)
-    assert same(a, want) and same(b, a)
+    assert same_bits(a, want) and same_bits(b, a)
     c = fr.run(rend, history=False)
-    assert same(c[:3], want[:3])
+    assert same_bits(c[:3], want[:3])
     assert 0 < (want[3] > 0).sum() < W * H and fr.prev_unchanged()
     # pixels without history: not one byte written (the call ran on the poisoned copy above as well)
     untouched = want[3] == 0
@@ -384,7 +374,7 @@ def test_other_stream_and_timing(rend):
     finally:
         rend.enable_timing(False)
     assert sample_ms > 0 and reduce_ms < 0.05 * sample_ms + 0.01
-    assert same(got, want)
+    assert same_bits(got, want)
     assert rend.kernel_name() == "temporal_accumulate"
 
 
@@ -448,10 +438,6 @@ def test_pixel_convention(rend):
 
 
 # ---- end to end: render_sequence on 96 x 54 images -------------------------------------------------------
-def rmse(a, b):
-    return float(np.sqrt(np.mean((np.asarray(a, np.float64) - b) ** 2)))
-
-
 def yardstick(cam, world):
     """A 2048-spp one-pass render of `cam` with a seed of its own."""
     c = copy_cam(cam)
@@ -481,13 +467,14 @@ def test_sequence_static_camera():
         assert f["image"].shape == (H, W, 3) and f["noisy"].shape == (H, W, 3) and f["variance"].shape == (H, W)
         assert f["counts"].dtype == np.uint32 and f["history"].dtype == np.uint32
     assert all((f["history"] == 0).all() and (f["counts"] == 4).all() for f in off)
-    assert (on[0]["history"] == 0).all() and same([on[0]["image"], on[0]["noisy"]], [off[0]["image"], off[0]["noisy"]])
+    assert (on[0]["history"] == 0).all() and same_bits([on[0]["image"], on[0]["noisy"]],
+                                                       [off[0]["image"], off[0]["noisy"]])
     # frames differ in their seeds: the baseline's frames are four different renders
     assert not np.array_equal(off[0]["noisy"], off[1]["noisy"])
     # the first frame is the one-pass render at its counts and seed
     c = copy_cam(cam.cam)
     c.samples_per_pixel, c.pixel_samples_scale = 4, 0.25
-    assert same([on[0]["noisy"]], [rtzig.render(c, world, n_gpus=1)])
+    assert same_bits([on[0]["noisy"]], [rtzig.render(c, world, n_gpus=1)])
     assert np.array_equal(on[3]["counts"], on[3]["history"] + 4)
     assert on[3]["history"].max() == 12  # three frames of 4 behind it, below max_history
     e_on, e_off = rmse(on[3]["image"], R), rmse(off[3]["image"], R)

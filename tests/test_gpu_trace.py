@@ -14,11 +14,12 @@ import torch
 
 import fast_scenes
 import rtzig
+from gpu_support import DEV, cached
+from gpu_support import module_renderers, renderers  # noqa: F401 (fixtures)
 from rtzig.lib import RtError
 
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 INF, NAN = math.inf, math.nan
 N = 4096
 FIELDS = ("index", "t", "point", "normal", "front")
@@ -59,16 +60,6 @@ def ref_hits(oracle, spheres, O, D, iv):
     return out
 
 
-_CACHE = {}
-
-
-def cached(key, make):
-    """A camera, a ray set or a reference, computed once per session and left unchanged."""
-    if key not in _CACHE:
-        _CACHE[key] = make()
-    return _CACHE[key]
-
-
 def final_cam():
     return cached("final_cam", lambda: rtzig.final_scene_camera(width=48, aspect_ratio=16 / 9, spp=2))
 
@@ -83,13 +74,6 @@ def share(ref):
 
 
 # ---- device helpers ----------------------------------------------------------------------------------
-def renderer(world, precision="f64"):
-    r = rtzig.DeviceRenderer(0)
-    r.set_scene(world)
-    r.set_precision(precision)
-    return r
-
-
 class Out:
     """The five device outputs of `cap` rays, pre-filled with sentinels."""
 
@@ -138,27 +122,25 @@ def assert_sentinel(got, start, fields=FIELDS):
 
 
 # ---- 1. base, all five outputs, BVH in LDS -----------------------------------------------------------
-def test_base_rays_all_outputs_bvh_in_lds(oracle):
+def test_base_rays_all_outputs_bvh_in_lds(oracle, renderers):
     O, D = cached("base_rays", base_rays)
     ref = base_ref(oracle)
     # input conditions
     assert abs(share(ref) - 0.4985) < 0.0006
     assert abs(float((ref["index"] == 0).mean()) - 0.377) < 0.0006  # the ground sphere
     assert len(set(ref["index"].tolist())) == 272  # 271 distinct spheres, and the miss
-    r = renderer(final_cam().scene.world)
-    try:
-        assert r.tree_info()["bvh"] == 1
-        got, stats = trace(r, O, D)
-        assert "(trace)" in r.kernel_name() and r.kernel_name().startswith("bvh_lds")
-        assert stats == [N, 0]
-        assert_equal(got, ref, label="base")
-        for n in (1, 63, 64, 65):
-            got, stats = trace(r, O[:128], D[:128], n=n)
-            assert stats == [n, 0]
-            assert_equal(got, ref, n=n, label="prefix %d" % n)
-            assert_sentinel(got, n)
-    finally:
-        r.close()
+    r = renderers(final_cam().scene.world)
+    assert r.tree_info()["bvh"] == 1
+    got, stats = trace(r, O, D)
+    assert "(trace)" in r.kernel_name() and r.kernel_name().startswith("bvh_lds")
+    assert stats == [N, 0]
+    assert_equal(got, ref, label="base")
+    for n in (1, 63, 64, 65):
+        got, stats = trace(r, O[:128], D[:128], n=n)
+        assert stats == [n, 0]
+        assert_equal(got, ref, n=n, label="prefix %d" % n)
+        assert_sentinel(got, n)
+    r.close()
 
 
 # ---- 2. intervals ------------------------------------------------------------------------------------
@@ -220,10 +202,8 @@ CASES = ["tmax2", "per_ray_tmax", "peel", "strict_tmax", "neg_all", "neg_5", "ne
 
 
 @pytest.fixture(scope="module")
-def final_renderer():
-    r = renderer(final_cam().scene.world)
-    yield r
-    r.close()
+def final_renderer(module_renderers):
+    return module_renderers(final_cam().scene.world)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -304,7 +284,7 @@ def test_direction_scale_ladder(oracle, final_renderer, e):
 
 
 # ---- 4. far origins ----------------------------------------------------------------------------------
-def test_far_origins_scan_then_tree_after_reserve(oracle):
+def test_far_origins_scan_then_tree_after_reserve(oracle, renderers):
     O, D = cached("base_rays", base_rays)
     Of = O * 400
     Df = -Of + D
@@ -312,80 +292,74 @@ def test_far_origins_scan_then_tree_after_reserve(oracle):
     ref = cached("far", lambda: ref_hits(oracle, cam.scene.world, Of, Df, intervals_of(N, 1e-3, INF)))
     assert 4798 < np.abs(Of).max() < 4800
     assert abs(share(ref) - 0.987) < 0.0015  # 4048 of 4096
-    r = renderer(cam.scene.world)
-    try:
-        # the tree's bound is the scene's extent, 2000 (the ground sphere: |c_y| + r).  Rays starting
-        # within it belong on the tree (rt_trace.h keeps them there), so the scan takes exactly the
-        # rays beyond it: most of the batch, and all of the sub-batch that lies beyond
-        bound = r.origin_bound()
-        assert 2000 <= bound < 2001
-        beyond = np.abs(Of).max(axis=1) > bound
-        assert beyond.mean() > 0.8
-        got, stats = trace(r, Of, Df)
-        assert stats == [N, int(beyond.sum())]
-        assert_equal(got, ref, label="far, scanned")
-        n_b = int(beyond.sum())
-        got_b, stats = trace(r, Of[beyond], Df[beyond])
-        assert stats == [n_b, n_b]
-        assert_equal(got_b, {f: ref[f][beyond] for f in FIELDS}, label="far, every ray scanned")
-        r.reserve_origin_bound(6000)
-        assert 6000 <= r.origin_bound() < 6100
-        got, stats = trace(r, Of, Df)
-        assert stats == [N, 0]
-        assert_equal(got, ref, label="far, tree")
-        bound = r.origin_bound()
-        r.reserve_origin_bound(100)  # smaller: a no-op
-        assert r.origin_bound() == bound
-        # the renderer on the rebuilt tree
-        W, H = cam.width, cam.height
-        img = torch.empty((H, W, 3), dtype=torch.float64, device=DEV)
-        r.render_rows_async(cam.cam, img.data_ptr())
-        torch.cuda.synchronize()
-        r.sync()
-        ref_img = cached("final48_b", lambda: oracle.render_b(cam.cam, cam.scene.world, threads=4)[0])
-        assert np.array_equal(img.cpu().numpy(), ref_img)
-    finally:
-        r.close()
+    r = renderers(cam.scene.world)
+    # the tree's bound is the scene's extent, 2000 (the ground sphere: |c_y| + r).  Rays starting
+    # within it belong on the tree (rt_trace.h keeps them there), so the scan takes exactly the
+    # rays beyond it: most of the batch, and all of the sub-batch that lies beyond
+    bound = r.origin_bound()
+    assert 2000 <= bound < 2001
+    beyond = np.abs(Of).max(axis=1) > bound
+    assert beyond.mean() > 0.8
+    got, stats = trace(r, Of, Df)
+    assert stats == [N, int(beyond.sum())]
+    assert_equal(got, ref, label="far, scanned")
+    n_b = int(beyond.sum())
+    got_b, stats = trace(r, Of[beyond], Df[beyond])
+    assert stats == [n_b, n_b]
+    assert_equal(got_b, {f: ref[f][beyond] for f in FIELDS}, label="far, every ray scanned")
+    r.reserve_origin_bound(6000)
+    assert 6000 <= r.origin_bound() < 6100
+    got, stats = trace(r, Of, Df)
+    assert stats == [N, 0]
+    assert_equal(got, ref, label="far, tree")
+    bound = r.origin_bound()
+    r.reserve_origin_bound(100)  # smaller: a no-op
+    assert r.origin_bound() == bound
+    # the renderer on the rebuilt tree
+    W, H = cam.width, cam.height
+    img = torch.empty((H, W, 3), dtype=torch.float64, device=DEV)
+    r.render_rows_async(cam.cam, img.data_ptr())
+    torch.cuda.synchronize()
+    r.sync()
+    ref_img = cached("final48_b", lambda: oracle.render_b(cam.cam, cam.scene.world, threads=4)[0])
+    assert np.array_equal(img.cpu().numpy(), ref_img)
+    r.close()
 
 
 # ---- 5. other structures -----------------------------------------------------------------------------
-def test_chapter13_list_walk_scans_every_ray(oracle):
+def test_chapter13_list_walk_scans_every_ray(oracle, renderers):
     cam = cached("ch13", lambda: rtzig.chapter13_camera(width=37))
     g = np.random.default_rng(5)
     O = g.uniform([-3, -0.4, -3], [3, 2, 1], (1000, 3))
     D = g.standard_normal((1000, 3))
     ref = cached("ch13_ref", lambda: ref_hits(oracle, cam.scene.world, O, D, intervals_of(1000, 1e-3, INF)))
     assert 0.3 < share(ref) < 0.9 and len(set(ref["index"].tolist())) == 6  # every sphere, and misses
-    r = renderer(cam.scene.world)
-    try:
-        assert r.tree_info()["bvh"] == 0 and r.origin_bound() == 0.0
-        got, stats = trace(r, O, D)
-        assert "(trace)" in r.kernel_name() and "bvh" not in r.kernel_name()
-        assert stats == [1000, 1000]
-        assert_equal(got, ref, label="chapter 13")
-    finally:
-        r.close()
+    r = renderers(cam.scene.world)
+    assert r.tree_info()["bvh"] == 0 and r.origin_bound() == 0.0
+    got, stats = trace(r, O, D)
+    assert "(trace)" in r.kernel_name() and "bvh" not in r.kernel_name()
+    assert stats == [1000, 1000]
+    assert_equal(got, ref, label="chapter 13")
+    r.close()
 
 
-def test_large_scene_global_memory_tree(oracle):
+def test_large_scene_global_memory_tree(oracle, renderers):
     cam = cached("large", fast_scenes.large)
     O, D = cached("base_rays", base_rays)
     O, D = O[:1024] * 2.5, D[:1024]
     ref = cached("large_ref", lambda: ref_hits(oracle, cam.scene.world, O, D, intervals_of(1024, 1e-3, INF)))
     assert 0.4 < share(ref) < 0.9 and len(set(ref["index"].tolist())) > 50
-    r = renderer(cam.scene.world)
-    try:
-        assert r.tree_info()["bvh"] == 1
-        got, stats = trace(r, O, D)
-        assert r.kernel_name() == "bvh_global(trace)"
-        assert stats == [1024, 0]
-        assert_equal(got, ref, label="large")
-    finally:
-        r.close()
+    r = renderers(cam.scene.world)
+    assert r.tree_info()["bvh"] == 1
+    got, stats = trace(r, O, D)
+    assert r.kernel_name() == "bvh_global(trace)"
+    assert stats == [1024, 0]
+    assert_equal(got, ref, label="large")
+    r.close()
 
 
 @pytest.mark.parametrize("precision, bvh", [("f64", 0), ("f32", 1)])
-def test_exact_duplicate_never_wins_and_zero_radius_sphere(oracle, precision, bvh):
+def test_exact_duplicate_never_wins_and_zero_radius_sphere(oracle, precision, bvh, renderers):
     """fast_scenes.materials(): sphere 5 is an exact copy of sphere 4, sphere 6 has radius 0.  Seven
     spheres walk the list on a parity context and the tree on an RT_PRECISION_F32 one (the trace itself is
     always parity arithmetic): the lowest index wins in both."""
@@ -398,34 +372,30 @@ def test_exact_duplicate_never_wins_and_zero_radius_sphere(oracle, precision, bv
     D[1000:] = [0.0, -1.0, 0.0]
     ref = cached("materials_ref", lambda: ref_hits(oracle, cam.scene.world, O, D, intervals_of(1024, 1e-3, INF)))
     assert (ref["index"][:512] == 4).mean() > 0.9 and not (ref["index"] == 5).any()
-    r = renderer(cam.scene.world, precision)
-    try:
-        assert r.tree_info()["bvh"] == bvh
-        got, stats = trace(r, O, D)
-        assert stats == [1024, 1024 * (1 - bvh)]
-        assert not (got["index"] == 5).any()
-        assert_equal(got, ref, label="materials " + precision)
-    finally:
-        r.close()
+    r = renderers(cam.scene.world, precision)
+    assert r.tree_info()["bvh"] == bvh
+    got, stats = trace(r, O, D)
+    assert stats == [1024, 1024 * (1 - bvh)]
+    assert not (got["index"] == 5).any()
+    assert_equal(got, ref, label="materials " + precision)
+    r.close()
 
 
 # ---- 6. tree independence ----------------------------------------------------------------------------
-def test_trained_tree_gives_the_same_bits(oracle, monkeypatch):
+def test_trained_tree_gives_the_same_bits(oracle, monkeypatch, renderers):
     O, D = cached("base_rays", base_rays)
     ref = base_ref(oracle)
     cam = final_cam()
     monkeypatch.setenv("RTZIG_BVH_TRAIN", "1")
-    r = renderer(cam.scene.world)
-    try:
-        img = torch.empty((cam.height, cam.width, 3), dtype=torch.float64, device=DEV)
-        r.render_rows_async(cam.cam, img.data_ptr())
-        torch.cuda.synchronize()
-        assert r.tree_info()["trained"] == 1
-        got, stats = trace(r, O, D)
-        assert stats == [N, 0]
-        assert_equal(got, ref, label="trained tree")
-    finally:
-        r.close()
+    r = renderers(cam.scene.world)
+    img = torch.empty((cam.height, cam.width, 3), dtype=torch.float64, device=DEV)
+    r.render_rows_async(cam.cam, img.data_ptr())
+    torch.cuda.synchronize()
+    assert r.tree_info()["trained"] == 1
+    got, stats = trace(r, O, D)
+    assert stats == [N, 0]
+    assert_equal(got, ref, label="trained tree")
+    r.close()
 
 
 # ---- 7. plumbing -------------------------------------------------------------------------------------
@@ -464,46 +434,40 @@ def test_non_default_stream_needs_no_host_sync(oracle, final_renderer):
 
 
 @pytest.mark.parametrize("kind", ["instrumented", "f32"])
-def test_instrumented_and_f32_contexts_give_the_same_bits(oracle, kind):
+def test_instrumented_and_f32_contexts_give_the_same_bits(oracle, kind, renderers):
     O, D = cached("base_rays", base_rays)
     ref = base_ref(oracle)
-    r = renderer(final_cam().scene.world, "f32" if kind == "f32" else "f64")
-    try:
-        if kind == "instrumented":
-            r.enable_profile(True)
-        got, stats = trace(r, O, D)
-        assert stats == [N, 0] and "(trace)" in r.kernel_name()
-        assert_equal(got, ref, label=kind)
-    finally:
-        r.close()
+    r = renderers(final_cam().scene.world, "f32" if kind == "f32" else "f64")
+    if kind == "instrumented":
+        r.enable_profile(True)
+    got, stats = trace(r, O, D)
+    assert stats == [N, 0] and "(trace)" in r.kernel_name()
+    assert_equal(got, ref, label=kind)
+    r.close()
 
 
-def test_kernel_times_and_empty_calls(oracle):
+def test_kernel_times_and_empty_calls(oracle, renderers):
     O, D = cached("base_rays", base_rays)
-    r = renderer(final_cam().scene.world)
-    try:
-        r.enable_timing(True)
-        trace(r, O[:256], D[:256])
-        sample_ms, reduce_ms = r.kernel_times()
-        assert sample_ms > 0 and reduce_ms == 0
-        name = r.kernel_name()
-        # n_rays == 0 and "nothing asked for" return RT_OK and launch nothing
-        out = Out(4)
-        r.trace_rays(1, 1, 0, **out.ptrs())          # the pointers are never read
-        r.trace_rays(1, 1, 4)
-        torch.cuda.synchronize()
-        assert_sentinel(out.host(), 0)
-        assert r.kernel_name() == name
-    finally:
-        r.close()
-    r = rtzig.DeviceRenderer(0)
-    try:
-        with pytest.raises(RtError, match="no scene"):
-            r.trace_rays(1, 1, 4, d_index_ptr=1)
-        with pytest.raises(RtError, match="no scene"):
-            r.reserve_origin_bound(10.0)
-    finally:
-        r.close()
+    r = renderers(final_cam().scene.world)
+    r.enable_timing(True)
+    trace(r, O[:256], D[:256])
+    sample_ms, reduce_ms = r.kernel_times()
+    assert sample_ms > 0 and reduce_ms == 0
+    name = r.kernel_name()
+    # n_rays == 0 and "nothing asked for" return RT_OK and launch nothing
+    out = Out(4)
+    r.trace_rays(1, 1, 0, **out.ptrs())          # the pointers are never read
+    r.trace_rays(1, 1, 4)
+    torch.cuda.synchronize()
+    assert_sentinel(out.host(), 0)
+    assert r.kernel_name() == name
+    r.close()
+    r = renderers()
+    with pytest.raises(RtError, match="no scene"):
+        r.trace_rays(1, 1, 4, d_index_ptr=1)
+    with pytest.raises(RtError, match="no scene"):
+        r.reserve_origin_bound(10.0)
+    r.close()
 
 
 # ---- 8. Python ---------------------------------------------------------------------------------------

@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 
 import rtzig
+from fast_scenes import golden_params
 from rtzig.abi import D3, RT_LAMBERTIAN, RtCameraParams
-from test_oracle import golden_params
 
 INF = math.inf
 

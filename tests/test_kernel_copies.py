@@ -17,12 +17,9 @@ always         2 + 4                            2 + 4
 handout        0 + 12                           0 + 8
 """
 import collections
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_build  # noqa: E402
+from abi_support import kernel_build
+
 KERNEL = "_ZN3rtk17sample_kernel_bvhILb1ELb0ELb0E"
 
 # region: (budget, the parent's count)

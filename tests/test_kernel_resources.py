@@ -3,21 +3,13 @@ no sample kernel uses scratch memory (a stray by-reference flag or dynamically i
 puts per-lane state in scratch: slower, and a spilling kernel faulted on the MI355X in round 4,
 profiles/r04_occupancy), and the uninstrumented BVH kernels keep 4 waves per SIMD (<= 128 VGPRs,
 DESIGN §5.1)."""
-import os
 import re
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_build  # noqa: E402
-
-
-def _resources():
-    return kernel_build.resources("rt_kernel.hip")
+from abi_support import resources
 
 
 def test_no_scratch_and_bvh_kernels_at_four_waves():
-    rows = _resources()
+    rows = resources("rt_kernel.hip")
     samples = {k: v for k, v in rows.items() if "sample_kernel" in k}
     assert len(samples) == 24, sorted(samples)
     assert all(v["ScratchSize [bytes/lane]"] == 0 for v in samples.values()), \

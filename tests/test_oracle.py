@@ -10,18 +10,12 @@ import os
 import numpy as np
 import pytest
 
-from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtCameraParams, RtSphere
+from fast_scenes import golden_params
+from gpu_support import box_rmse
 from oracle_lib import read_ppm
+from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtCameraParams, RtSphere
 
 INF = math.inf
-
-
-def golden_params(width=400, aspect=16.0 / 9.0, spp=10, seed=0xDEADBEEF):
-    # main.zig:24-31 preset
-    return RtCameraParams(image_width=width, samples_per_pixel=spp, bounce_max=50,
-                          aspect_ratio=aspect, look_from=D3(13, 2, 3), look_at=D3(0, 0, 0),
-                          v_up=D3(0, 1, 0), vfov=20, defocus_angle=0.6, focus_dist=10,
-                          t_min=1e-3, t_max=INF, seed=seed)
 
 
 def test_golden_chapter14_byte_exact(oracle, golden_dir):
@@ -203,11 +197,6 @@ def test_config1_normals_antialiased_statistical(oracle, golden_dir):
     assert (np.abs(rgb - gold).max(axis=2) <= 2).mean() >= 0.98
 
 
-def _box_rmse(a, b):
-    box = lambda x: x[:224].reshape(28, 8, 50, 8, 3).astype(np.float64).mean(axis=(1, 3))
-    return float(np.sqrt(((box(a) - box(b)) ** 2).mean()))
-
-
 @pytest.mark.parametrize("config", ["chapter9", "chapter13"])
 def test_presets_statistically_match_reference_images(oracle, golden_dir, config):
     """Configs 2 and 3 have no byte-exact pin: the reference's images/chapter9.ppm and
@@ -221,9 +210,9 @@ def test_presets_statistically_match_reference_images(oracle, golden_dir, config
     b, _ = oracle.render_b(cam.cam, cam.scene.world, threads=8)
     A, B = oracle.to_rgb8(a), oracle.to_rgb8(b)
     _, _, gold = read_ppm(open(os.path.join(golden_dir, f"{config}.ppm"), "rb").read())
-    floor = _box_rmse(A, B)
+    floor = box_rmse(A, B)
     assert np.abs(B.astype(np.float64).mean(axis=(0, 1)) - gold.astype(np.float64).mean(axis=(0, 1))).max() <= 1.0
-    assert _box_rmse(B, gold) <= 1.5 * floor, (_box_rmse(B, gold), floor)
+    assert box_rmse(B, gold) <= 1.5 * floor, (box_rmse(B, gold), floor)
 
 
 # ---- oracle_accumulate_b: a sample range added onto stored sums ----------------------------------

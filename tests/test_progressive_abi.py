@@ -4,37 +4,28 @@ argument checks answer before anything touches a device, and the ABI version did
 import ctypes as C
 
 import rtzig
+from abi_support import assert_bound, assert_invalid, vp
 from rtzig.abi import RtCamera
-from rtzig.lib import EXPORTED
-
-RT_ERR_INVALID = -1
 
 
 def test_symbols_exported_and_bound():
-    lib = rtzig.load()
-    for name in ("rt_render_rows_accumulate", "rt_accum_resolve"):
-        assert name in EXPORTED
-        fn = getattr(lib, name)
-        assert fn.restype is C.c_int and fn.argtypes is not None
-    assert len(lib.rt_render_rows_accumulate.argtypes) == 10
-    assert len(lib.rt_accum_resolve.argtypes) == 7
+    assert_bound("rt_render_rows_accumulate", 10)
+    assert_bound("rt_accum_resolve", 7)
 
 
 def test_accumulate_null_context_is_invalid():
     lib = rtzig.load()
     cam = RtCamera()
     buf = (C.c_double * 3)()
-    rc = lib.rt_render_rows_accumulate(None, C.byref(cam), 0, 1, 1, 0, 1, C.cast(buf, C.c_void_p), None, None)
-    assert rc == RT_ERR_INVALID
-    assert b"context" in lib.rt_last_error()
+    rc = lib.rt_render_rows_accumulate(None, C.byref(cam), 0, 1, 1, 0, 1, vp(buf), None, None)
+    assert_invalid(rc, b"context")
 
 
 def test_resolve_null_context_is_invalid():
     lib = rtzig.load()
     a, o = (C.c_double * 3)(), (C.c_double * 3)()
-    rc = lib.rt_accum_resolve(None, C.cast(a, C.c_void_p), 1, 1, 0, C.cast(o, C.c_void_p), None)
-    assert rc == RT_ERR_INVALID
-    assert b"context" in lib.rt_last_error()
+    rc = lib.rt_accum_resolve(None, vp(a), 1, 1, 0, vp(o), None)
+    assert_invalid(rc, b"context")
 
 
 def test_abi_version_unchanged():

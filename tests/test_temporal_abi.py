@@ -8,31 +8,23 @@ import ctypes as C
 import inspect
 import os
 import re
-import sys
 
 import numpy as np
 import pytest
 
 import rtzig
 import temporal_ref
-from rtzig.abi import RtCamera, RtTemporalFrame, RtTemporalParams
-from rtzig.lib import EXPORTED
+from abi_support import RT_ERR_INVALID, ROOT, assert_bound, assert_invalid, cam_of, resources
+from rtzig.abi import RtTemporalFrame, RtTemporalParams
 
-RT_ERR_INVALID = -1
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_build  # noqa: E402
 DEFAULTS = dict(max_history=64, reserved=0, sigma_z=0.05, tau_n=0.1, tau_a=0.05, tau_h=0.5, min_weight=0.25)
 
 
 def test_symbols_exported_bound_and_declared():
-    lib = rtzig.load()
     with open(os.path.join(ROOT, "include", "rt.h")) as f:
         header = f.read()
     for name, nargs in (("rt_temporal_accumulate", 8), ("rt_temporal_default_params", 1)):
-        assert name in EXPORTED
-        fn = getattr(lib, name)
-        assert fn.restype is C.c_int and len(fn.argtypes) == nargs
+        assert_bound(name, nargs)
         assert re.search(r"\bint %s\(" % name, header)
     assert "typedef struct rt_temporal_frame" in header and "typedef struct rt_temporal_params" in header
     assert "Only the first frame" in header  # the header says what is bit-identical to a one-pass render
@@ -60,18 +52,6 @@ def test_struct_sizes_and_default_params():
     assert {k: v for k, v in DEFAULTS.items() if k != "reserved"} == temporal_ref.DEFAULTS
 
 
-def _cam(w=4, h=3):
-    """A camera whose du x dv is not 0 and whose centre lies off its image plane."""
-    cam = RtCamera()
-    cam.image_width, cam.image_height, cam.samples_per_pixel, cam.bounce_max = w, h, 1, 1
-    for k in range(3):
-        cam.center[k] = 0.0
-        cam.pixel0[k] = (-0.5, 0.5, -1.0)[k]
-        cam.du[k] = (0.25, 0.0, 0.0)[k]
-        cam.dv[k] = (0.0, -0.25, 0.0)[k]
-    return cam
-
-
 def _frame(base, **over):
     """rt_temporal_frame of made-up non-null pointers (never dereferenced: a null context answers last)."""
     f = dict(accum=1, m2=2, counts=3, albedo=4, normal=5, depth=6, hits=7)
@@ -84,7 +64,7 @@ def _frame(base, **over):
 
 def temporal_call(ctx=None, cam="ok", cam_prev="ok", cur=None, prev=None, params=None, null=(), history=1):
     lib = rtzig.load()
-    a = dict(cam=_cam() if cam == "ok" else cam, cam_prev=_cam() if cam_prev == "ok" else cam_prev,
+    a = dict(cam=cam_of() if cam == "ok" else cam, cam_prev=cam_of() if cam_prev == "ok" else cam_prev,
              cur=_frame(0, **(cur or {})), prev=_frame(16, **(prev or {})))
     ref = {k: (None if k in null else C.byref(v)) for k, v in a.items()}
     return lib.rt_temporal_accumulate(ctx, ref["cam"], ref["cur"], ref["cam_prev"], ref["prev"],
@@ -93,7 +73,7 @@ def temporal_call(ctx=None, cam="ok", cam_prev="ok", cur=None, prev=None, params
 
 
 def _cam_with(**kw):
-    cam = _cam(kw.pop("w", 4), kw.pop("h", 3))
+    cam = cam_of(kw.pop("w", 4), kw.pop("h", 3))
     for name, v in kw.items():
         for k in range(3):
             getattr(cam, name)[k] = v[k]
@@ -157,8 +137,7 @@ def test_invalid_arguments_answer_without_a_device(name):
     kw = dict(kw)
     if "params" in kw:
         kw["params"] = rtzig.temporal_params(**kw["params"])
-    assert temporal_call(**kw) == RT_ERR_INVALID
-    assert word in rtzig.load().rt_last_error(), rtzig.load().rt_last_error()
+    assert_invalid(temporal_call(**kw), word)
 
 
 def test_limits_that_pass_the_checks():
@@ -168,8 +147,7 @@ def test_limits_that_pass_the_checks():
     for kw in (dict(params=rtzig.temporal_params(max_history=1)), dict(params=rtzig.temporal_params(max_history=2 ** 24)),
                dict(params=rtzig.temporal_params(sigma_z=0.0, tau_n=0.0, tau_a=0.0, tau_h=0.0)),
                dict(params=rtzig.temporal_params(min_weight=1.0)), big):
-        assert temporal_call(**kw) == RT_ERR_INVALID
-        assert b"context" in rtzig.load().rt_last_error()
+        assert_invalid(temporal_call(**kw), b"context")
 
 
 def test_python_entry_points_and_signatures():
@@ -194,22 +172,18 @@ def test_python_entry_points_and_signatures():
                                 dict(spp=4, feature_spp=-1), dict(spp=4, output="hdr"), dict(spp=4, precision="f16"),
                                 dict(spp=4, temporal=dict(max_history=4)), dict(spp=4, temporal=rtzig.denoise_params()),
                                 dict(spp=4, denoise=rtzig.temporal_params()), dict(spp=4, cams=[]),
-                                dict(spp=4, cams=[_cam(), _cam(5, 3)]), dict(spp=4, cams=[_cam(0, 3)]),
+                                dict(spp=4, cams=[cam_of(), cam_of(5, 3)]), dict(spp=4, cams=[cam_of(0, 3)]),
                                 dict(spp=4, cams=["camera"])])
 def test_render_sequence_rejects_bad_arguments_before_any_device_work(kw):
     kw = dict(kw)
-    cams = kw.pop("cams", [_cam(), _cam()])
+    cams = kw.pop("cams", [cam_of(), cam_of()])
     with pytest.raises(ValueError):
         rtzig.render_sequence(cams, [], **kw)  # at the call, not at the first next(); an empty scene: never reached
 
 
 # ---- the kernel's resources (build time) ---------------------------------------------------------------
-def _resources():
-    return kernel_build.resources("rt_temporal.hip")
-
-
 def test_one_temporal_kernel_without_scratch_or_lds():
-    rows = _resources()
+    rows = resources("rt_temporal.hip")
     assert len(rows) == 1 and "temporal_accumulate_kernel" in next(iter(rows)), sorted(rows)
     v = next(iter(rows.values()))
     assert v["ScratchSize [bytes/lane]"] == 0 and v["LDS Size [bytes/block]"] == 0, v
@@ -239,7 +213,7 @@ def test_reference_identical_cameras_take_min_of_counts_and_cap():
     passes too — history == min(counts', max_history) at every hit pixel, 0 at the sky pixel — and the
     merged mean is the previous mean."""
     W, H = 3, 2
-    cam = _cam(W, H)
+    cam = cam_of(W, H)
     prev = _smooth(W, H, [24, 24, 24, 24, 24, 24], fs=8)
     cur = _smooth(W, H, [0, 4, 4, 4, 4, 4])
     cur["accum"][0], cur["m2"][0] = np.nan, np.nan  # counts 0: not read
@@ -255,7 +229,7 @@ def test_reference_identical_cameras_take_min_of_counts_and_cap():
 
 def test_reference_without_previous_samples_changes_nothing():
     W, H = 3, 2
-    cam = _cam(W, H)
+    cam = cam_of(W, H)
     prev = _smooth(W, H, [0] * 6, fs=8)
     cur = _smooth(W, H, [0, 4, 4, 4, 4, 4])
     cur["accum"][0], cur["m2"][0] = np.nan, np.nan

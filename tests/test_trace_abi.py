@@ -8,28 +8,18 @@ import inspect
 import math
 import os
 import re
-import sys
 
 import pytest
 
 import rtzig
+from abi_support import ROOT, assert_bound, assert_invalid, resources, vp
 from rtzig import abi
-from rtzig.lib import EXPORTED
-
-RT_OK = 0
-RT_ERR_INVALID = -1
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import kernel_build  # noqa: E402
 
 
 @pytest.mark.parametrize("name, n_args", [("rt_trace_rays", 11), ("rt_context_origin_bound", 2),
                                           ("rt_context_reserve_origin_bound", 2)])
 def test_symbols_exported_bound_and_declared(name, n_args):
-    lib = rtzig.load()
-    assert name in EXPORTED
-    fn = getattr(lib, name)
-    assert fn.restype is C.c_int and len(fn.argtypes) == n_args
+    assert_bound(name, n_args)
     with open(os.path.join(ROOT, "include", "rt.h")) as f:
         m = re.search(r"\bint %s\(([^;]*)\);" % name, f.read())
     assert m and len(m.group(1).split(",")) == n_args
@@ -47,8 +37,8 @@ def trace_call(ctx=None, origins="ok", directions="ok", out="ok", stride=3, n=4)
     lib = rtzig.load()
     o, d = (C.c_double * 16)(), (C.c_double * 16)()
     hits = abi.RtRayHits()
-    return lib.rt_trace_rays(ctx, C.cast(o, C.c_void_p) if origins == "ok" else None,
-                             C.cast(d, C.c_void_p) if directions == "ok" else None, stride, n, 1e-3, math.inf, None,
+    return lib.rt_trace_rays(ctx, vp(o) if origins == "ok" else None,
+                             vp(d) if directions == "ok" else None, stride, n, 1e-3, math.inf, None,
                              C.byref(hits) if out == "ok" else None, None, None)
 
 
@@ -67,29 +57,24 @@ def trace_call(ctx=None, origins="ok", directions="ok", out="ok", stride=3, n=4)
 ], ids=["ctx", "ctx-empty", "ctx-stride0", "ctx-stride4", "origins", "directions", "out", "stride1", "stride2",
         "n-2^32", "n-2^63"])
 def test_invalid_arguments_answer_without_a_device(kw, word):
-    assert trace_call(**kw) == RT_ERR_INVALID
-    assert word in rtzig.load().rt_last_error()
+    assert_invalid(trace_call(**kw), word)
 
 
 def test_largest_ray_count_passes_the_count_check():
-    assert trace_call(n=2 ** 32 - 1) == RT_ERR_INVALID
-    assert b"context" in rtzig.load().rt_last_error()
+    assert_invalid(trace_call(n=2 ** 32 - 1), b"context")
 
 
 @pytest.mark.parametrize("bound", [0.0, -1.0, math.inf, -math.inf, math.nan, 1.79e308])  # the last: x 1.01 overflows
 def test_reserve_origin_bound_rejects_bad_bounds_before_the_context(bound):
     lib = rtzig.load()
-    assert lib.rt_context_reserve_origin_bound(None, bound) == RT_ERR_INVALID
-    assert b"bound" in lib.rt_last_error()
+    assert_invalid(lib.rt_context_reserve_origin_bound(None, bound), b"bound")
 
 
 def test_bound_calls_reject_a_null_context():
     lib = rtzig.load()
-    assert lib.rt_context_reserve_origin_bound(None, 10.0) == RT_ERR_INVALID
-    assert b"context" in lib.rt_last_error()
+    assert_invalid(lib.rt_context_reserve_origin_bound(None, 10.0), b"context")
     b = C.c_double()
-    assert lib.rt_context_origin_bound(None, C.byref(b)) == RT_ERR_INVALID
-    assert b"context" in lib.rt_last_error()
+    assert_invalid(lib.rt_context_origin_bound(None, C.byref(b)), b"context")
 
 
 def test_python_entry_points_and_signatures():
@@ -126,7 +111,7 @@ def test_trace_rays_rejects_bad_shapes_before_any_device_work():
 
 # ---- the trace kernels' register budget (build time) -----------------------------------------------
 def test_four_trace_kernels_no_scratch_bvh_ones_fit_a_1024_thread_block():
-    rows = kernel_build.resources("rt_kernel.hip")
+    rows = resources("rt_kernel.hip")
     trace = {k: v for k, v in rows.items() if re.search(r"trace_kernel(_bvh)?I", k)}
     # the list walk (lds, smem) and the BVH walk (LDS tree, global-memory tree)
     assert len(trace) == 4, sorted(trace)
