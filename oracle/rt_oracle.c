@@ -582,6 +582,25 @@ EXPORT void oracle_random_u64(uint64_t seed, size_t count, uint64_t* out) {
     for (size_t k = 0; k < count; k++) out[k] = xoshiro_next(&g);
 }
 
+/* The same streams from a caller's state: the four state words of DefaultPrng.init(key), and the
+ * words / Random.float(f64) draws of a generator started in state[4] (not modified), so that
+ * seed_state followed by a state function equals the seeded function above. */
+EXPORT void oracle_seed_state(uint64_t key, uint64_t* out) {
+    xoshiro g;
+    xoshiro_seed(&g, key);
+    memcpy(out, g.s, sizeof g.s);
+}
+EXPORT void oracle_random_u64_state(const uint64_t* state, size_t count, uint64_t* out) {
+    xoshiro g;
+    memcpy(g.s, state, sizeof g.s);
+    for (size_t k = 0; k < count; k++) out[k] = xoshiro_next(&g);
+}
+EXPORT void oracle_random_doubles_state(const uint64_t* state, size_t count, double* out) {
+    xoshiro g;
+    memcpy(g.s, state, sizeof g.s);
+    for (size_t k = 0; k < count; k++) out[k] = rd(&g);
+}
+
 /* Vec.refract / Vec.reflect KATs (vec.zig:103-112) */
 EXPORT void oracle_reflect(const double* v, const double* n, double* out) {
     const v3 r = reflect(V(v[0], v[1], v[2]), V(n[0], n[1], n[2]));

@@ -82,6 +82,9 @@ struct SharedRcp {
         const double y1 = __builtin_fma(y0, __builtin_fma(-den, y0, 1.0), y0);
         y = __builtin_fma(y1, __builtin_fma(-den, y1, 1.0), y1);
     }
+    // x / l for x and the quotient in the unscaled range, or x = +0.0.  Not for x = -0.0: the residual
+    // -0 + +0 is +0 and the sign is lost (the scatter finish's numerators are range_pm1 values, whose
+    // only zero is +0.0; RayDiv sends every zero down the full division).
     __device__ __forceinline__ double div(double x) const {
         const double q0 = x * y;
         return __builtin_fma(__builtin_fma(-l, q0, x), y, q0);
@@ -340,7 +343,8 @@ struct RngT {
     __device__ __forceinline__ double range(double mn, double mx) { return mn + (mx - mn) * uniform(); }
     // range(-1, 1): (1 - -1) * u = 2u is exact, so -1 + 2u has ONE rounding and fma(2, u, -1) gives
     // the same bits with one f64 op instead of two (u may be subnormal: 2u is still exact).
-    __device__ __forceinline__ double range_pm1() { return __builtin_fma(2.0, uniform(), -1.0); }
+    __device__ __forceinline__ static double pm1_of(double u) { return __builtin_fma(2.0, u, -1.0); }
+    __device__ __forceinline__ double range_pm1() { return pm1_of(uniform()); }
 };
 using Rng = RngT<true>;
 

@@ -44,6 +44,9 @@ class Oracle:
         L.oracle_world_hit.restype = C.c_long
         L.oracle_random_doubles.argtypes = [C.c_uint64, C.c_size_t, dp]
         L.oracle_random_u64.argtypes = [C.c_uint64, C.c_size_t, P(C.c_uint64)]
+        L.oracle_seed_state.argtypes = [C.c_uint64, P(C.c_uint64)]
+        L.oracle_random_u64_state.argtypes = [P(C.c_uint64), C.c_size_t, P(C.c_uint64)]
+        L.oracle_random_doubles_state.argtypes = [P(C.c_uint64), C.c_size_t, dp]
         L.oracle_render_book.argtypes = [C.c_int, C.c_uint32, C.c_double, P(C.c_uint8), P(C.c_uint32)]
         L.oracle_reflect.argtypes = [dp, dp, dp]
         L.oracle_refract.argtypes = [dp, dp, C.c_double, dp]
@@ -182,6 +185,28 @@ class Oracle:
     def random_u64(self, seed, n):
         out = np.zeros(n, np.uint64)
         self.L.oracle_random_u64(seed, n, out.ctypes.data_as(P(C.c_uint64)))
+        return out
+
+    def seed_state(self, key):
+        """The four Xoshiro256++ state words of DefaultPrng.init(key), as a uint64 array."""
+        out = np.zeros(4, np.uint64)
+        self.L.oracle_seed_state(key, out.ctypes.data_as(P(C.c_uint64)))
+        return out
+
+    def random_u64_state(self, state, n):
+        """The next n words of a generator in `state` (4 words; not modified)."""
+        st = np.ascontiguousarray(state, np.uint64)
+        assert st.shape == (4,)
+        out = np.zeros(n, np.uint64)
+        self.L.oracle_random_u64_state(st.ctypes.data_as(P(C.c_uint64)), n, out.ctypes.data_as(P(C.c_uint64)))
+        return out
+
+    def random_doubles_state(self, state, n):
+        """The next n Random.float(f64) draws of a generator in `state` (4 words; not modified)."""
+        st = np.ascontiguousarray(state, np.uint64)
+        assert st.shape == (4,)
+        out = np.zeros(n)
+        self.L.oracle_random_doubles_state(st.ctypes.data_as(P(C.c_uint64)), n, out.ctypes.data_as(dp))
         return out
 
     def reflect(self, v, n):

@@ -1,0 +1,639 @@
+"""What the tests of the device primitives share (tests/test_gpu_primitives.py on the GPU,
+tests/test_probe_inputs.py on the CPU): the loader of the probe library (tests/hip/rt_probe.hip,
+built as raytracing-with-zig_amd/librtzig_probe.so), the input generators and the numpy references.
+
+References are plain numpy f64 under np.errstate(all="ignore"): x86 sqrt and / are correctly rounded
+and numpy never contracts a*b+c.  A helper module, not a test: every assert carries its own message.
+"""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "raytracing-with-zig_amd")
+PROBE_SO = os.path.join(PKG, "librtzig_probe.so")
+LEAF_CPP = os.path.join(ROOT, "tests", "cpp", "test_leaf_filter.cpp")
+
+OPS = dict(sqrt=0, unit=1, unit_accepted=2, raydiv=3, reflect=4, refract=5, range_pm1=6, sample_key=7,
+           seed_words=8, state_words_lean=9, state_words_full=10, state_uniform_lean=11,
+           state_uniform_full=12, leaf_behind=13, mul_rcp=14)
+LANES = (0, 31, 32, 63)  # where the one special value of a wave is put
+U64 = np.uint64
+M52 = (1 << 52) - 1
+
+
+# ---- the probe library -----------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def load():
+    """The probe library (built first if its .so is missing, like conftest does for the others)."""
+    if not os.path.exists(PROBE_SO):
+        subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "../librtzig_probe.so"], check=True,
+                       stdout=subprocess.DEVNULL)
+    L = C.CDLL(PROBE_SO)
+    L.rt_probe_run.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32,
+                               C.c_void_p]
+    L.rt_probe_run.restype = C.c_int
+    L.rt_probe_planes.argtypes = [C.c_int] + [C.POINTER(C.c_int)] * 4
+    L.rt_probe_planes.restype = C.c_int
+    L.rt_probe_no_draw.restype = C.c_uint64
+    return L
+
+
+def planes(op):
+    """(input planes, output planes, output planes are per draw, output is bytes) of an op."""
+    v = [C.c_int() for _ in range(4)]
+    rc = load().rt_probe_planes(OPS[op], *[C.byref(x) for x in v])
+    assert rc == 0, f"unknown op {op}"
+    return v[0].value, v[1].value, bool(v[2].value), bool(v[3].value)
+
+
+def no_draw():
+    return U64(load().rt_probe_no_draw())
+
+
+def run(op, *cols, k=0):
+    """Runs `op` on GPU 0 over the input planes `cols` (equal-length f64 / uint64 arrays).  The planes
+    are padded to whole blocks of 256 with their first element.  Returns the output planes cut back to
+    the input length: an (planes, n) array of the inputs' dtype, or (n,) uint8 for a byte op."""
+    import torch
+
+    n_in, n_out, per_draw, byte_out = planes(op)
+    assert len(cols) == n_in, f"{op} takes {n_in} planes, got {len(cols)}"
+    n = len(cols[0])
+    dtype = cols[0].dtype
+    assert n > 0 and all(len(c) == n and c.dtype.itemsize == 8 for c in cols), "planes of 8-byte elements"
+    pad = -n % 256
+    host = np.empty((n_in, n + pad), np.int64)
+    for p, c in enumerate(cols):
+        v = np.ascontiguousarray(c).view(np.int64)
+        host[p, :n] = v
+        host[p, n:] = v[0]
+    np_ = n + pad
+    n_out = k if per_draw else n_out
+    with torch.cuda.device(0):
+        d_in = torch.from_numpy(host).to("cuda:0")
+        d_out = torch.zeros((np_,), dtype=torch.uint8, device="cuda:0") if byte_out else \
+            torch.zeros((n_out, np_), dtype=torch.int64, device="cuda:0")
+        stream = torch.cuda.current_stream()
+        rc = load().rt_probe_run(OPS[op], d_in.data_ptr(), d_in.numel() * 8, d_out.data_ptr(),
+                                 d_out.numel() * d_out.element_size(), np_, k, stream.cuda_stream)
+        assert rc == 0, f"rt_probe_run({op}) returned {rc}"
+        stream.synchronize()
+        out = d_out.cpu().numpy()
+    return out[:n].copy() if byte_out else out[:, :n].copy().view(dtype)
+
+
+# ---- comparison ------------------------------------------------------------------------------------------
+def mismatches(got, want):
+    """Indices (flat) where two f64 arrays differ: as int64 bits, so the sign of zero and of inf count;
+    where the reference is a NaN the device's must be one too, payload and sign not compared."""
+    got, want = np.ascontiguousarray(got, np.float64), np.ascontiguousarray(want, np.float64)
+    assert got.shape == want.shape, f"shapes {got.shape} and {want.shape}"
+    nan = np.isnan(want)
+    bad = np.where(nan, ~np.isnan(got), got.view(np.int64) != want.view(np.int64))
+    return np.flatnonzero(bad)
+
+
+def describe(bad, got, want, *cols):
+    """A message for the first few mismatches: inputs, device and reference as hex floats."""
+    lines = [f"{len(bad)} of {np.size(want)} differ"]
+    g, w = np.ravel(got), np.ravel(want)
+    n = len(cols[0]) if cols else 1
+    for i in bad[:8]:
+        ins = " ".join(float(c[i % n]).hex() for c in cols)
+        lines.append(f"  [{i}] in {ins}: device {float(g[i]).hex()} reference {float(w[i]).hex()}")
+    return "\n".join(lines)
+
+
+# ---- building blocks -------------------------------------------------------------------------------------
+def f64(bits):
+    return np.asarray(bits, U64).view(np.float64)
+
+
+def mant(rng, n):
+    """n doubles in [1, 2) with 52 random mantissa bits."""
+    return f64(rng.integers(0, 1 << 52, n, dtype=U64) | U64(1023 << 52))
+
+
+def scaled(rng, n, lo, hi):
+    """m * 2^e, m in [1, 2), e uniform in [lo, hi]."""
+    return np.ldexp(mant(rng, n), rng.integers(lo, hi + 1, n).astype(np.int32))
+
+
+def signs(rng, n):
+    return np.where(rng.integers(0, 2, n) == 1, -1.0, 1.0)
+
+
+def nudge(x, k):
+    """x moved k ulps away from zero (k < 0: towards it); for finite x far from 0 and inf."""
+    b = np.asarray(x, np.float64).view(np.int64)
+    return (b + np.int64(k)).view(np.float64)
+
+
+def from_fields(sign, exp, mantissa):
+    return f64((U64(sign) << U64(63)) | (np.asarray(exp, U64) << U64(52)) | np.asarray(mantissa, U64))
+
+
+def _exact_round(num, shift):
+    """fl(num * 2^-shift) for a Python int `num`: int / int is correctly rounded in CPython."""
+    return num / (1 << shift) if shift >= 0 else float(num << -shift)
+
+
+# ---- division --------------------------------------------------------------------------------------------
+BIG = np.finfo(np.float64).max
+DIV_A_EDGES = np.array([2.0 ** -100, np.nextafter(2.0 ** -100, 0), 2.0 ** 100, np.nextafter(2.0 ** 100, np.inf),
+                        1.0, 0.0, -1.0, np.inf, np.nan, 2.0 ** -1074, BIG])
+DIV_X_EXPS = (0, 1, 422, 423, 1622, 1623, 2046, 2047)
+
+
+def div_random(n=1 << 15, seed=101):
+    """(a) a = m * 2^e, e in [-100, 100]; x = +-m' * 2^f, f in [-600, 599]."""
+    rng = np.random.default_rng(seed)
+    return scaled(rng, n, -100, 100), signs(rng, n) * scaled(rng, n, -600, 599)
+
+
+def _aq(rng, n):
+    """Divisors a (inside the guard) and 53-bit quotients q as (mantissa int, exponent) pairs."""
+    ma = rng.integers(1 << 52, 1 << 53, n, dtype=U64)
+    mq = rng.integers(1 << 52, 1 << 53, n, dtype=U64)
+    ea = rng.integers(-99, 100, n)
+    eq = rng.integers(-400, 401, n)
+    return ma, ea, mq, eq
+
+
+def _q(mq, eq, x0):
+    return np.copysign(np.ldexp(mq.astype(np.float64), (eq - 52).astype(np.int32)), x0)
+
+
+def div_near_representable(n=1 << 13, seed=102, with_q=False):
+    """(b) x = fl(a*q) and its neighbours at -2..+2 ulp, q a random 53-bit number: quotients that lie
+    on or next to a representable number.  5n elements."""
+    rng = np.random.default_rng(seed)
+    ma, ea, mq, eq = _aq(rng, n)
+    a = np.ldexp(ma.astype(np.float64), (ea - 52).astype(np.int32))
+    x0 = np.array([_exact_round(int(p) * int(q), 0) for p, q in zip(ma, mq)])
+    x0 = np.ldexp(x0, (ea + eq - 104).astype(np.int32)) * signs(rng, n)
+    x = np.concatenate([nudge(x0, k) for k in (-2, -1, 0, 1, 2)])
+    return (np.tile(a, 5), x, _q(mq, eq, x0)) if with_q else (np.tile(a, 5), x)
+
+
+def div_near_midpoint(n=1 << 13, seed=103, with_q=False):
+    """(c) x = fl(a*q + a*ulp(q)/2) and its neighbours at +-1 ulp: quotients next to the midpoint of
+    two representable numbers, where the last step's rounding decides.  3n elements."""
+    rng = np.random.default_rng(seed)
+    ma, ea, mq, eq = _aq(rng, n)
+    a = np.ldexp(ma.astype(np.float64), (ea - 52).astype(np.int32))
+    x0 = np.array([_exact_round(int(p) * (2 * int(q) + 1), 0) for p, q in zip(ma, mq)])  # a * (q + ulp/2) * 2
+    x0 = np.ldexp(x0, (ea + eq - 105).astype(np.int32)) * signs(rng, n)
+    x = np.concatenate([nudge(x0, k) for k in (-1, 0, 1)])
+    return (np.tile(a, 3), x, _q(mq, eq, x0)) if with_q else (np.tile(a, 3), x)
+
+
+def div_guard_edges(seed=104, randoms=2):
+    """(d) the full cross product a edge x biased exponent of x x mantissa {0, all ones, random} x sign.
+    Returns (a, x, classes) with classes[i] = (index of a, exponent, mantissa kind, sign)."""
+    rng = np.random.default_rng(seed)
+    a, x, cls = [], [], []
+    for ia, av in enumerate(DIV_A_EDGES):
+        for e in DIV_X_EXPS:
+            for kind in [0, 1] + [2] * randoms:
+                m = (0, M52, int(rng.integers(1, M52)))[kind]
+                for s in (0, 1):
+                    a.append(av)
+                    x.append(from_fields(s, e, m))
+                    cls.append((ia, e, kind, s))
+    return np.array(a), np.array(x, np.float64), cls
+
+
+def div_extreme_results(n=1 << 10, seed=105):
+    """(e) divisions on the slow path whose results overflow, underflow or go subnormal: the exponent
+    of x minus that of a around +1024 and around -1022 .. -1080, from a out of range and from x out of
+    range with a inside the guard."""
+    rng = np.random.default_rng(seed)
+    q = n // 4
+    out_a, out_x = [], []
+    for gap_lo, gap_hi, side in ((1015, 1030, -1), (-1090, -1015, 1)):  # overflow: small a; underflow: large a
+        for lo, hi in ((101, 500), (16, 99)):  # a outside the guard; a inside it and x far outside its range
+            ea = side * rng.integers(lo, hi + 1, q)
+            ex = ea + rng.integers(gap_lo, gap_hi + 1, q)
+            assert ex.min() >= -1074 and ex.max() <= 1023, "exponents of x"
+            out_a.append(np.ldexp(mant(rng, q), ea.astype(np.int32)))
+            out_x.append(signs(rng, q) * np.ldexp(mant(rng, q), ex.astype(np.int32)))
+    return np.concatenate(out_a), np.concatenate(out_x)
+
+
+def div_ordinary(n, seed=106):
+    """In-range operands only: a in [2^-99, 2^100), the biased exponent of x in [423, 1623)."""
+    rng = np.random.default_rng(seed)
+    return scaled(rng, n, -99, 99), signs(rng, n) * scaled(rng, n, -600, 599)
+
+
+def div_ref(a, x):
+    with np.errstate(all="ignore"):
+        return x / a
+
+
+def mul_rcp_ref(a, x):
+    with np.errstate(all="ignore"):
+        return x * (1.0 / a)
+
+
+# ---- sqrt ------------------------------------------------------------------------------------------------
+SQRT_GUARD = U64(0x10000000 << 32)  # 2^-767
+
+
+def sqrt_random(n=1 << 15, seed=201):
+    """Positive finite doubles, biased exponent uniform over [0, 2046]."""
+    rng = np.random.default_rng(seed)
+    return from_fields(0, rng.integers(0, 2047, n), rng.integers(0, 1 << 52, n, dtype=U64))
+
+
+def sqrt_near_squares(n=1 << 13, seed=202):
+    """fl(q*q) and its neighbours at -2..+2 ulp (roots next to a representable number), then
+    fl((q + ulp/2)^2) and its neighbours at +-1 ulp (roots next to a midpoint).  8n elements."""
+    rng = np.random.default_rng(seed)
+    mq = rng.integers(1 << 52, 1 << 53, n, dtype=U64)
+    eq = rng.integers(-390, 501, n)
+    sq = np.ldexp(np.array([_exact_round(int(q) * int(q), 0) for q in mq]), (2 * eq - 104).astype(np.int32))
+    mid = np.ldexp(np.array([_exact_round((2 * int(q) + 1) ** 2, 0) for q in mq]), (2 * eq - 106).astype(np.int32))
+    return np.concatenate([nudge(sq, k) for k in (-2, -1, 0, 1, 2)] + [nudge(mid, k) for k in (-1, 0, 1)])
+
+
+def sqrt_edges():
+    """The guard at 2^-767 (one ulp below, on, one ulp above), the far end of the range, and the
+    specials: subnormals, the smallest normal, +-0, negatives, +-inf, NaN, the largest finite."""
+    g = int(SQRT_GUARD)
+    bits = [g - 1, g, g + 1, g - 2, g + 2,
+            0x7fefffffffffffff, 0x7fe0000000000000, 0x7ff0000000000000, 0xfff0000000000000, 0x7ff8000000000000,
+            0x7ff0000000000001, 0, 1 << 63, 1, 2, M52, 0x000fffffffffffff, 0x0010000000000000, 0x0010000000000001,
+            0x0008000000000000, 0x00000000ffffffff, 0x0000000100000000]
+    neg = [-1.0, -4.0, -2.0 ** -1074, -2.0 ** -767, -BIG, -2.0 ** -1022]
+    return np.concatenate([f64(np.array(bits, U64)), np.array(neg)])
+
+
+def sqrt_ordinary(n, seed=203):
+    rng = np.random.default_rng(seed)
+    return scaled(rng, n, -700, 1000)
+
+
+def sqrt_ref(x):
+    with np.errstate(all="ignore"):
+        return np.sqrt(x)
+
+
+# ---- lane layouts ----------------------------------------------------------------------------------------
+def one_special_lane(ordinary, special):
+    """Waves of 63 ordinary values and one special value: every special value at lane 0, 31, 32 and 63
+    in turn.  `ordinary` and `special` are tuples of equal-length planes.  Returns (planes, index of each
+    special element in the planes)."""
+    n_ord, n_spec = len(ordinary[0]), len(special[0])
+    waves = len(LANES) * n_spec
+    pick = (np.arange(waves * 64) % n_ord).reshape(waves, 64)
+    lane = np.repeat(np.array(LANES), n_spec)
+    at = np.arange(waves) * 64 + lane
+    out = []
+    for o, s in zip(ordinary, special):
+        v = np.asarray(o)[pick].reshape(-1).copy()
+        v[at] = np.tile(s, len(LANES))
+        out.append(v)
+    return tuple(out), at
+
+
+def whole_waves(special):
+    """The special values alone, padded with themselves to whole waves of 64."""
+    n = len(special[0])
+    idx = np.arange(n + (-n % 64)) % n
+    return tuple(np.asarray(s)[idx] for s in special)
+
+
+def layouts(sets, edge_sets, ordinary):
+    """The three layouts of a family of input sets: {"order": every set in generator order,
+    "one_special": the edge sets one value per wave among ordinary ones, "waves": the edge sets as
+    whole waves}.  Each set is a tuple of planes."""
+    cat = lambda ss: tuple(np.concatenate([s[p] for s in ss]) for p in range(len(ss[0])))
+    special = cat(edge_sets)
+    return {"order": cat(sets), "one_special": one_special_lane(ordinary, special)[0], "waves": whole_waves(special)}
+
+
+@functools.lru_cache(maxsize=None)
+def div_layouts():
+    edges = div_guard_edges()[:2]
+    extreme = div_extreme_results()
+    sets = [div_random(), div_near_representable(), div_near_midpoint(), edges, extreme]
+    return layouts(sets, [edges, extreme], div_ordinary(4096))
+
+
+@functools.lru_cache(maxsize=None)
+def sqrt_layouts():
+    edges = (np.concatenate([sqrt_edges(), sqrt_near_squares(64, seed=204)]),)
+    sets = [(sqrt_random(),), (sqrt_near_squares(),), edges]
+    return layouts(sets, [edges], (sqrt_ordinary(4096),))
+
+
+# ---- vectors ---------------------------------------------------------------------------------------------
+def len_sq(v):
+    return (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+
+
+def dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _directions(rng, n):
+    v = rng.standard_normal((3, n))
+    return v / np.sqrt((v * v).sum(axis=0))
+
+
+def unit_inputs(n=1 << 14, seed=301):
+    """(3, N): random directions of length about 2^e, e in [-383, 511], with the edge vectors spread
+    among them (one every 64 elements, moving through the lanes)."""
+    rng = np.random.default_rng(seed)
+    v = _directions(rng, n) * np.ldexp(1.0, rng.integers(-383, 512, n).astype(np.int32))
+    t, z, inf = 2.0 ** -384, 0.0, np.inf
+    edges = [(t, t, z), (t, z, z), (z, z, z), (-z, z, -z), (2.0 ** 600, z, z), (2.0 ** 511, 2.0 ** 511, 2.0 ** 511),
+             (inf, 1.0, 1.0), (1.0, -inf, z), (z, t, t), (nudge(t, -1), t, z), (nudge(t, 1), t, z), (np.nan, 1.0, 1.0),
+             (2.0 ** -1074, z, z), (2.0 ** -537, 2.0 ** -537, z), (2.0 ** 511, 2.0 ** 511, z), (-t, -t, z)]
+    e = np.array(edges).T
+    reps = 4 * len(LANES)
+    at = (np.arange(len(edges) * reps) * 64 + np.tile(np.repeat(np.array(LANES), len(edges)), 4)) % n
+    v[:, at] = np.tile(e, (1, reps))
+    return v
+
+
+def unit_ref(v):
+    with np.errstate(all="ignore"):
+        return v * (1.0 / np.sqrt(len_sq(v)))
+
+
+def accepted(p):
+    ls = len_sq(p)
+    return (1e-160 < ls) & (ls <= 1)
+
+
+def unit_accepted_inputs(oracle, n=1 << 14, seed=302):
+    """(3, N) points that randomUnitVec accepts (1e-160 < |p|^2 <= 1): real range_pm1 values of an
+    oracle stream, then |p|^2 = 1 exactly, zero components, components of +-2^-52 and the documented
+    domain down to components of 1e-80.  A zero component is +0.0: range_pm1 gives no other, since
+    fma(2, 0.5, -1) is +0.0 in round-to-nearest, and the scatter finish's short division is not defined
+    for -0.0 (it would return +0.0 where the true division keeps the sign)."""
+    rng = np.random.default_rng(seed)
+    u = oracle.random_doubles(seed, 3 * 2 * n).reshape(3, -1)
+    real = -1.0 + 2.0 * u
+    real = real[:, accepted(real)][:, :n]
+    pts = []
+    for ax in range(3):
+        for s in (1.0, -1.0):
+            p = [0.0, 0.0, 0.0]
+            p[ax] = s
+            pts.append(p)
+            p = [0.0, 0.0, 0.0]
+            p[ax] = s * 0.5
+            pts.append(p)
+    e = 2.0 ** -52
+    for sx in (e, -e):
+        for sy in (e, -e, 0.0, 0.75):
+            for sz in (e, -e, 0.0, -0.5):
+                pts.append([sx, sy, sz])
+    pts += [[0.6, 0.8, 0.0], [0.0, -0.6, 0.8], [2.0 ** -1, 2.0 ** -1, 2.0 ** -1], [1.0, 2.0 ** -53, 0.0]]
+    edge = np.array(pts).T
+    # the small end of the domain: components m * 10^-k, k up to 80, alone and next to ordinary ones
+    m = 4096
+    small = rng.uniform(1.0, 9.9, (3, m)) * 10.0 ** -rng.integers(0, 81, (3, m)) * rng.choice([-1.0, 1.0], (3, m))
+    small[1, ::3] = 0.0
+    small[:, 1::7] = rng.uniform(1.01, 9.9, (3, len(small[0, 1::7]))) * 1e-80
+    out = np.concatenate([real, edge, small], axis=1)
+    assert not (np.signbit(out) & (out == 0)).any(), "no -0.0 component"
+    return np.ascontiguousarray(out[:, accepted(out)])
+
+
+def unit_accepted_ref(p):
+    with np.errstate(all="ignore"):
+        return p / np.sqrt(len_sq(p))
+
+
+def reflect_ref(v, n):
+    with np.errstate(all="ignore"):
+        return v - (n * dot(v, n)) * 2.0
+
+
+def refract_ref(v, n, eta):
+    with np.errstate(all="ignore"):
+        cos_t = np.fmin(dot(-v, n), 1.0)
+        r_perp = (v + n * cos_t) * eta
+        r_par = n * -np.sqrt(np.fabs(1.0 - len_sq(r_perp)))
+        return r_perp + r_par
+
+
+def refract_inputs(n=1 << 16, seed=303):
+    """(v (3, N), n (3, N), eta (N,)): random unit v and n with eta in [0.4, 2.5]; v = -n; v
+    perpendicular to n with eta at and next to 1, where |r_perp|^2 is 1 (sqrt of 0: the slow path) or
+    just above 1 (the fabs branch)."""
+    rng = np.random.default_rng(seed)
+    v, nn = _directions(rng, n), _directions(rng, n)
+    eta = rng.uniform(0.4, 2.5, n)
+    q = n // 8
+    v[:, :q] = -nn[:, :q]
+    axes = np.eye(3)
+    etas = [1.0, 1.0 + 2.0 ** -52, 1.0 + 2.0 ** -26, 1.0 - 2.0 ** -53, 1.25, 2.5]
+    vs, ns, es = [], [], []
+    for i in range(3):
+        for j in range(3):
+            if i == j:
+                continue
+            for sv in (1.0, -1.0):
+                for sn in (1.0, -1.0):
+                    for e in etas:
+                        vs.append(sv * axes[i])
+                        ns.append(sn * axes[j])
+                        es.append(e)
+    for e in etas:  # a 3-4-5 direction: 0.36 + 0.64 rounds to 1 or just above
+        vs.append(np.array([0.6, 0.8, 0.0]))
+        ns.append(np.array([0.0, 0.0, 1.0]))
+        es.append(e)
+    m = len(es)
+    reps = len(LANES)
+    at = (np.arange(m * reps) * 64 + np.repeat(np.array(LANES), m)) % (n - q) + q
+    v[:, at] = np.tile(np.array(vs).T, (1, reps))
+    nn[:, at] = np.tile(np.array(ns).T, (1, reps))
+    eta[at] = np.tile(np.array(es), reps)
+    return v, nn, eta, at
+
+
+def range_pm1_inputs(oracle, n=1 << 14, seed=304):
+    """u of Random.float(f64): real draws, then the ends and the rounding edges of -1 + 2u."""
+    u = oracle.random_doubles(seed, n)
+    edge = [0.0, 2.0 ** -1074, 2.0 ** -1022, 2.0 ** -60, 2.0 ** -54, 2.0 ** -53, 3 * 2.0 ** -55, 0.25, 0.5,
+            np.nextafter(0.5, 0), np.nextafter(0.5, 1), 1.0 - 2.0 ** -53, 0.75, np.nextafter(0.25, 0)]
+    rng = np.random.default_rng(seed)
+    small = mant(rng, 1024) * np.ldexp(1.0, -rng.integers(1, 80, 1024).astype(np.int32))  # 52 bits below 0.5
+    return np.concatenate([u, np.array(edge), small])
+
+
+def range_pm1_ref(u):
+    return -1.0 + 2.0 * u
+
+
+# ---- RNG -------------------------------------------------------------------------------------------------
+M64 = (1 << 64) - 1
+
+
+def rotl(x, k):
+    return ((x << k) | (x >> (64 - k))) & M64
+
+
+def rotr(x, k):
+    return rotl(x, 64 - k)
+
+
+def clz64(w):
+    return 64 - int(w).bit_length()
+
+
+def key_cases(n=4096, seed=401):
+    """(seed, pixel, sample) triples: seeds with and without bit 63, pixel in {0, 1, 2^31, 2^32-1},
+    sample in {0, 2^31, 2^32-1}, every combination."""
+    rng = np.random.default_rng(seed)
+    combos = [(p, s) for p in (0, 1, 1 << 31, (1 << 32) - 1) for s in (0, 1 << 31, (1 << 32) - 1)]
+    seeds = rng.integers(0, 1 << 64, n, dtype=U64)
+    seeds[::2] |= U64(1 << 63)
+    seeds[1::2] &= U64((1 << 63) - 1)
+    seeds[:4] = np.array([0, 1, M64, 1 << 63], U64)
+    pix = np.array([combos[i % 12][0] for i in range(n)], U64)
+    smp = np.array([combos[i % 12][1] for i in range(n)], U64)
+    return seeds, pix, smp
+
+
+def is_rare(words):
+    """A word with >= 12 leading zeros: Random.float's slow path."""
+    return np.asarray(words, U64) < U64(1 << 52)
+
+
+def rare_keys(oracle, want=128, draws=64, start=1 << 40):
+    """Keys whose first `draws` words contain a rare word, found with the oracle (about 1 in 64)."""
+    out, key = [], start
+    while len(out) < want:
+        if is_rare(oracle.random_u64(key, draws)).any():
+            out.append(key)
+        key += 1
+        assert key < start + 400 * want, "rare keys are about 1 in 64"
+    return np.array(out, U64)
+
+
+def state_first_word(word, rng):
+    """A random state whose first word is `word`: next() returns rotl(s0 + s3, 23) + s0."""
+    s0, s1, s2 = (int(x) for x in rng.integers(0, 1 << 64, 3, dtype=U64))
+    s3 = (rotr((word - s0) & M64, 23) - s0) & M64
+    return [s0, s1, s2, s3]
+
+
+def state_t_zero(t, a=0):
+    """s0 = 0, s1 = s3 = rotr(T, 23), s2 = s1 ^ A: the words are T, 0 and then, with A = 0, a second 0
+    and a fourth word set by T alone; with A != 0 the third word is rotl(A + rotl(A, 45), 23) + A."""
+    s1 = rotr(t, 23)
+    return [0, s1, s1 ^ a, s1]
+
+
+def third_word(a):
+    return (rotl((a + rotl(a, 45)) & M64, 23) + a) & M64
+
+
+def fourth_word(t):
+    s1 = rotr(t, 23)
+    b = s1 ^ ((s1 << 17) & M64)
+    return (rotl((b + rotl(b, 45)) & M64, 23) + b) & M64
+
+
+def deep_states(seed=402):
+    """Injected states that force Random.float's deep path, as (states (N, 4) uint64, the leading
+    words each is built to give: a list of tuples).  Found by search over T < 2^52 (and A) for a given
+    number of leading zeros in the word that ends the run of zeros."""
+    rng = np.random.default_rng(seed)
+    states, words = [], []
+    states.append([0, 0, 0, 0])  # every word 0: lz clamps at 1022, the result is +0.0
+    words.append((0,) * 17)
+    for lz in (0, 1, 5, 11, 12, 13):  # T, 0, 0, then a word with lz leading zeros
+        for _ in range(4):
+            while True:
+                t = int(rng.integers(1, 1 << 52))
+                if clz64(fourth_word(t)) == lz:
+                    break
+            states.append(state_t_zero(t))
+            words.append((t, 0, 0, fourth_word(t)))
+    for lz in (0, 3, 11, 12, 14):  # T, 0, then a word with lz leading zeros
+        for _ in range(4):
+            while True:
+                a = int(rng.integers(1, 1 << 64, dtype=U64))
+                if clz64(third_word(a)) == lz:
+                    break
+            t = int(rng.integers(1, 1 << 52))
+            states.append(state_t_zero(t, a))
+            words.append((t, 0, third_word(a)))
+    for lz in (11, 12):  # a first word with exactly 11 (fast path) and exactly 12 (rare) leading zeros
+        for _ in range(8):
+            w = int(rng.integers(0, 1 << (63 - lz))) | (1 << (63 - lz))
+            states.append(state_first_word(w, rng))
+            words.append((w,))
+    for w in (0, 1, (1 << 52) - 1, 1 << 52, (1 << 44) - 1, 1 << 32, (1 << 32) - 1, 1 << 31):  # 32-bit halves
+        states.append(state_first_word(w, rng))
+        words.append((w,))
+    return np.array(states, U64), words
+
+
+def ordinary_states(n, seed=403):
+    return np.random.default_rng(seed).integers(1, 1 << 64, (n, 4), dtype=U64)
+
+
+def draw_masks(kind, n, steps, seed=404):
+    """Per-lane masks: bit k set = the lane draws at step k.  "all": every step; "trip": the trip
+    loop's pattern, every third draw made only by the lanes whose bit is set; "random"."""
+    rng = np.random.default_rng(seed)
+    full = U64((1 << steps) - 1)
+    if kind == "all":
+        return np.full(n, full, U64)
+    r = rng.integers(0, 1 << 64, n, dtype=U64) & full
+    if kind == "random":
+        return r
+    assert kind == "trip", kind
+    third = U64(sum(1 << k for k in range(2, steps, 3)))
+    return (full & ~third) | (r & third)
+
+
+def masked_stream(stream, masks, steps, sentinel):
+    """What the masked probe must write: lane i's stream consumed only at the set bits of its mask,
+    `sentinel` elsewhere.  stream: (N, steps) uint64; returns (steps, N) uint64."""
+    n = len(masks)
+    out = np.full((steps, n), sentinel, U64)
+    used = np.zeros(n, np.int64)
+    rows = np.arange(n)
+    for k in range(steps):
+        on = ((masks >> U64(k)) & U64(1)).astype(bool)
+        out[k, on] = stream[rows[on], used[on]]
+        used += on
+    return out
+
+
+def state_streams(oracle, states, steps):
+    """(words (N, steps), Random.float draws as bits (N, steps)) of each state, from the oracle."""
+    w = np.array([oracle.random_u64_state(s, steps) for s in states])
+    d = np.array([oracle.random_doubles_state(s, steps) for s in states]).view(U64)
+    return w, d
+
+
+# ---- leaf filter -----------------------------------------------------------------------------------------
+def build_leaf_filter_host(tmp_dir):
+    """Compiles tests/cpp/test_leaf_filter.cpp (the host side of rt_leaf_filter.h); returns the program."""
+    exe = os.path.join(str(tmp_dir), "test_leaf_filter")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", LEAF_CPP, "-o", exe], check=True)
+    return exe
+
+
+def leaf_filter_cases(exe, tmp_dir, n=1 << 16):
+    """n cases of the host test's families and the host's answers: ((4, n) f64, (n,) uint8)."""
+    path = os.path.join(str(tmp_dir), "leaf_cases.bin")
+    subprocess.run([exe, "dump", str(n), path], check=True, timeout=120)
+    raw = np.fromfile(path, np.uint8)
+    assert raw.size == 33 * n, f"dump of {raw.size} bytes"
+    return raw[:32 * n].view(np.float64).reshape(4, n), raw[32 * n:]
