@@ -514,6 +514,45 @@ typedef struct rt_ray_hits {   /* DEVICE pointers; each may be NULL: that output
 int rt_trace_rays(rt_context* ctx, const void* d_origins, const void* d_directions,
                   uint32_t ray_stride, uint64_t n_rays, double t_min, double t_max,
                   const void* d_intervals, const rt_ray_hits* out, void* d_stats, void* stream);
+/* ---- occlusion queries: any hit of caller-supplied rays, bit-exact ----------------
+ * Ray q is OCCLUDED iff HittableList.hit(ray_q, Interval(t_min_q, t_max_q)) returns true in the
+ * reference's f64 arithmetic — equivalently, iff some sphere's own Sphere.hit(ray, (t_min, t_max)) is
+ * true (a sphere that the shrinking `closest` rejects is rejected only after another was accepted, and
+ * an accepted root lies in (t_min, t_max) by the reference's strict comparisons).  So the answer equals
+ * rt_trace_rays' index >= 0 for every input that call accepts — NaN, infinities, zero directions,
+ * negative or inverted intervals, duplicate spheres and zero radii included — and no sphere order,
+ * tree or early exit changes it.  The walk stops at the first accepted root, its interval never
+ * shrinks, and it writes 1 byte and / or 1 bit per ray.
+ *
+ * d_origins, d_ends, ray_stride, d_intervals, t_min, t_max: exactly as rt_trace_rays (stride in doubles,
+ * 0 means 3, 1 and 2 are invalid).  Without a flag d_ends holds directions, used as given.  With
+ * RT_OCCLUSION_TARGETS it holds end points: the direction is end - origin, computed on the device with
+ * one f64 subtraction per component, and the natural interval is (eps, 1.0), the open segment.
+ * Interval.surrounds is strict, so an occluder whose root is exactly 1.0 — exactly at the end point —
+ * does not count.  Any other flag bit: RT_ERR_INVALID (the message names `flags`).
+ *
+ * d_occluded ([n] uint8, may be NULL): 1 or 0 for every ray.
+ * d_mask ([ceil(n / 64)] uint64, may be NULL): bit q & 63 of word q >> 6 is set iff ray q is occluded.
+ *   Every word is written whole; the bits past n in the last word are 0; words past ceil(n / 64) are
+ *   not touched.
+ * d_stats (DEVICE, 3 x uint64, may be NULL) is atomically incremented: [0] rays, [1] rays the list scan
+ *   resolved, [2] occluded rays.
+ *
+ * Always parity arithmetic; instrumented and RT_PRECISION_F32 contexts are accepted; the structure the
+ * context holds is walked as it is, never rebuilt or trained.  The tree's domain rule is
+ * rt_trace_rays' (csrc/rt_trace.h), applied to the ray as used: after the subtraction in targets mode.
+ * Rays outside it are answered by an early-exit scan of the whole list: the same answer.
+ *
+ * Launch: asynchronous on `stream`, one kernel, a plain one-stream call, no workspace;
+ * rt_context_kernel_times reports it as sample_ms, with reduce_ms 0.  n_rays == 0: RT_OK, nothing is
+ * touched.  Both outputs NULL and d_stats NULL: RT_OK, no launch.
+ * RT_ERR_INVALID, each answered before any device is touched: null d_origins or d_ends; ray_stride 1
+ * or 2; n_rays >= 2^32; unknown flags; null ctx; no scene uploaded. */
+#define RT_OCCLUSION_TARGETS 1u   /* d_ends holds end points: dir_k = end_k - origin_k, one f64 subtraction per component */
+int rt_occluded_rays(rt_context* ctx, const void* d_origins, const void* d_ends,
+                     uint32_t ray_stride, uint64_t n_rays, double t_min, double t_max,
+                     const void* d_intervals, uint32_t flags,
+                     uint8_t* d_occluded, uint64_t* d_mask, void* d_stats, void* stream);
 /* The origin bound of the tree the context holds: rays starting within it (max|o_k| <= bound) may use
  * the tree; rays starting beyond it are exact but cost a scan of the whole list.  0 when the list walk
  * runs. */

@@ -186,6 +186,24 @@ struct TraceArgs {
     uint32_t n_tiles;          // set by rtk_launch_trace: tiles of 64 rays, a wave each
     uint32_t pad;
 };
+// Occlusion queries (rt_occluded_rays): is ray q occluded, i.e. does HittableList.hit
+// return true?  Rays and intervals as TraceArgs; with `targets` != 0 `ends` holds end points and the
+// direction is ends[q] - origins[q], one f64 subtraction per component.  The occlusion kernels
+// (occlusion_kernel*, rt_kernel.hip) take this as their LAST argument, as the trace kernels do.
+struct OcclusionArgs {
+    const double* origins;
+    const double* ends;        // directions, or end points (targets)
+    const double* intervals;   // [n][2] or nullptr
+    uint8_t* occluded;         // [n] 1 / 0, or nullptr
+    unsigned long long* mask;  // [ceil(n / 64)] bit q & 63 of word q >> 6, or nullptr
+    unsigned long long* stats; // {rays, rays resolved by the list scan, occluded rays} or nullptr
+    unsigned long long* ctr;   // kCtrBytes: [kErrWord] error word (RTZIG_BOUNDS debug builds)
+    double t_min, t_max;
+    uint32_t n_rays;           // > 0
+    uint32_t ray_stride;       // doubles between rays, >= 3
+    uint32_t targets;          // RT_OCCLUSION_TARGETS
+    uint32_t n_tiles;          // set by rtk_launch_occlusion: tiles of 64 rays, a wave each
+};
 // rt_accum_select: an ordered stream compaction in three launches, none of which
 // waits on another block.  Blocks of kSelBlock threads, one pixel each.  Scratch (the context's):
 // [blocks] u32 block counts (the scan turns them into exclusive offsets in place), then, 8-B aligned,
@@ -429,6 +447,10 @@ extern "C" hipError_t rtk_launch_features(const rtk::KernelParams* p, const rtk:
 extern "C" hipError_t rtk_launch_trace(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
                                        const rtk::MatRec* mat, const rtk::TraceArgs* ta, hipStream_t stream,
                                        const char** name);
+// Occlusion queries (rtk::OcclusionArgs): the occlusion kernel of the structure the context holds,
+// chosen and sized exactly as rtk_launch_trace chooses the trace kernel.  One launch, no workspace.
+extern "C" hipError_t rtk_launch_occlusion(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                           const rtk::OcclusionArgs* oa, hipStream_t stream, const char** name);
 // rt_accum_select's three launches (count, scan, scatter) over a->n pixels.
 extern "C" hipError_t rtk_launch_select(const rtk::SelectArgs* a, hipStream_t stream);
 // out[q] = accum[q] * (1.0 / counts[q]) (0 where counts[q] == 0), formats as rtk_launch_resolve.

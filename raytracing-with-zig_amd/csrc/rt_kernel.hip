@@ -48,6 +48,12 @@
 //   run trace_loop — one lane per caller-supplied ray, its own interval, the whole hit record.  A ray
 //   outside the domain the tree's f32 boxes are certified for (rt_trace.h) takes the list scan.  The
 //   walkers are used as they are; the existing kernels compile to the same instructions as before.
+//
+// Occlusion queries (rt_occluded_rays, rt_kernel.h OcclusionArgs): occlusion_kernel (list walk) and
+//   occlusion_kernel_bvh run occlusion_loop — one lane per ray, one boolean out — through the walkers'
+//   any-hit mode (BvhWalker::any_hit, world_any): the interval never shrinks and a lane leaves at its
+//   first accepted root.  Routing as the trace kernels.  New entry points only; the existing kernels
+//   compile to the same instructions as before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -346,6 +352,43 @@ __device__ __forceinline__ int world_hit(const GeoRec* __restrict__ geo, uint32_
     return best;
 }
 
+// world_hit's any-hit sibling (rt_occluded_rays): does HittableList.hit return true?
+// The same discriminant chains in list order, U at a time, and Sphere.hit's own root selection against
+// the interval as given — `closest` never moves, since a sphere that the shrinking `closest` rejects
+// is rejected only after another one was accepted.  A lane leaves at its first accepted root.
+template <int U>
+__device__ __forceinline__ bool world_any(const GeoRec* __restrict__ geo, uint32_t n_pad, const Ray& r, double t_min,
+                                          double t_max) {
+    const double a = len_sq(r.dir);
+    for (uint32_t k = 0; k < n_pad; k += U) {
+        double h[U], disc[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const GeoRec s = geo[k + u];
+            const double ocx = s.cx - r.orig.x;
+            const double ocy = s.cy - r.orig.y;
+            const double ocz = s.cz - r.orig.z;
+            h[u] = (r.dir.x * ocx + r.dir.y * ocy) + r.dir.z * ocz;
+            const double c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.r2;
+            disc[u] = h[u] * h[u] - a * c;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (disc[u] >= 0) {
+                const double sq = sqrt_g(disc[u]);
+                double root = (h[u] - sq) / a;
+                bool ok = t_min < root && root < t_max;
+                if (!ok) {
+                    root = (h[u] + sq) / a;
+                    ok = t_min < root && root < t_max;
+                }
+                if (ok) return true;
+            }
+        }
+    }
+    return false;
+}
+
 // x / l for several numerators x sharing one denominator l, bit-identical to the compiler's
 // correctly rounded f64 division (v_div_scale, v_rcp_f64, two Newton steps, q0 = x*y,
 // r = fma(-l, q0, x), v_div_fmas = fma(r, y, q0), v_div_fixup) whenever that sequence does not
@@ -479,6 +522,12 @@ struct LinearWalker {
     __device__ __forceinline__ int run(const Ray& r, double t_min, double t_max, double* t, PR& pr, State&, bool,
                                        bool = true) const {
         return (*this)(r, t_min, t_max, t, pr);
+    }
+    // any-hit (occlusion_loop): world_any over the same list
+    template <class PR>
+    __device__ __forceinline__ bool any_hit(const Ray& r, double t_min, double t_max, PR& pr) const {
+        pr.tests(n_real);
+        return world_any<U>(geo, n_pad, r, t_min, t_max);
     }
 };
 
@@ -1234,6 +1283,138 @@ struct BvhWalker {
         }
         *t_hit = closest;
         return found ? (int)best : -1;
+    }
+
+    // ---- any-hit mode of the parity walk (rt_occluded_rays) ----------------------
+    // Is there a sphere whose Sphere.hit(r, (t_min, t_max)) is true?  run_f64's walk with `closest`
+    // frozen at t_max: no best, no tie-break, `upper` computed once, and a lane leaves the walk the
+    // moment a root is accepted.  No suspension (the query kernels never refetch).
+
+    // candidate()'s root selection for a sphere with disc >= 0, against the fixed interval: root1, then
+    // root2 only when !(t_min < root1) (root2 >= root1: a root1 at or past t_max has no root2 inside)
+    template <int Q, class PR>
+    __device__ __forceinline__ static bool accepted(double h, double disc, const RayDiv& a, double t_min, double t_max, PR& pr) {
+        pr.template cand_block<Q>();
+        const double sq = sqrt_g(disc);
+        double ts = a.div(h - sq);
+        bool cand = t_min < ts;
+        if (!cand) {
+            pr.template root2_block<Q>();
+            ts = a.div(h + sq);
+            cand = t_min < ts;
+        }
+        return cand && ts < t_max;
+    }
+    // test_always_geo without the index
+    template <int Q, class PR>
+    __device__ __forceinline__ static bool always_any_geo(const u32x8& w, const Ray& r, double a, const RayDiv& ad, double t_min,
+                                                          double t_max, const LeafFilter& lfilt, PR& pr) {
+        const GeoRec s{dw2d(w[0], w[1]), dw2d(w[2], w[3]), dw2d(w[4], w[5]), dw2d(w[6], w[7])};
+        const double ocx = s.cx - r.orig.x;
+        const double ocy = s.cy - r.orig.y;
+        const double ocz = s.cz - r.orig.z;
+        const double h = (r.dir.x * ocx + r.dir.y * ocy) + r.dir.z * ocz;
+        const double c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.r2;
+        const double disc = h * h - a * c;
+        return disc >= 0 && !lfilt.behind(h, disc) && accepted<Q>(h, disc, ad, t_min, t_max, pr);
+    }
+    // test_always_c's scalar loads (the pointer from the kernarg segment, the sphere at an immediate offset)
+    template <int Q, class PR>
+    __device__ __forceinline__ bool always_any_c(const Ray& r, double a, const RayDiv& ad, double t_min, double t_max,
+                                                 const LeafFilter& lfilt, PR& pr) const {
+        constexpr int kGeoPtr = 336 + 16;  // test_always_c's static_assert
+        const uint64_t kp = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
+        uint64_t pg;
+        asm volatile("s_load_dwordx2 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(pg) : "s"(kp), "i"(kGeoPtr));
+        u32x8 w;
+        asm volatile("s_load_dwordx8 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(pg), "i"(Q * 32));
+        return always_any_geo<Q>(w, r, a, ad, t_min, t_max, lfilt, pr);
+    }
+    template <class PR>
+    __device__ __forceinline__ bool any_hit(const Ray& r, double t_min, double t_max, PR& pr) const {
+        static_assert(!kF32, "parity arithmetic only");
+        const double a = len_sq(r.dir);
+        const LeafFilter lfilt = LeafFilter::make(a, t_min);
+        const RayDiv ad(a);
+        // the always-list first: a lane occluded there never enters the tree
+        bool occ = false;
+        if (n_always <= 4) {
+            if (n_always_now() > 0) occ = always_any_c<0>(r, a, ad, t_min, t_max, lfilt, pr);
+            if (n_always_now() > 1 && !occ) occ = always_any_c<1>(r, a, ad, t_min, t_max, lfilt, pr);
+            if (n_always_now() > 2 && !occ) occ = always_any_c<2>(r, a, ad, t_min, t_max, lfilt, pr);
+            if (n_always_now() > 3 && !occ) occ = always_any_c<3>(r, a, ad, t_min, t_max, lfilt, pr);
+        } else {
+            for (uint32_t q = 0; q < n_always; ++q) {
+                u32x8 w;
+                asm volatile("s_load_dwordx8 %0, %1, 0\n\ts_waitcnt lgkmcnt(0)" : "=s"(w) : "s"(ageo + q));
+                if (!occ) occ = always_any_geo<-1>(w, r, a, ad, t_min, t_max, lfilt, pr);
+            }
+        }
+        pr.tests(n_always);
+        // the f32 ray, the slab constants and the far-origin rule: run_f64's, which see
+        const float ox = (float)r.orig.x, oy = (float)r.orig.y, oz = (float)r.orig.z;
+        const float dx = (float)r.dir.x, dy = (float)r.dir.y, dz = (float)r.dir.z;
+        const float ix = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dx), -1e30f, 1e30f);
+        const float iy = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dy), -1e30f, 1e30f);
+        const float iz = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dz), -1e30f, 1e30f);
+        const uint32_t ax = ix < 0 ? 8u : 0u, ay = 16u + (iy < 0 ? 8u : 0u), az = 32u + (iz < 0 ? 8u : 0u);
+        const bool far = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ox), __builtin_fabsf(oy)), __builtin_fabsf(oz)) >
+                         origin_bound;
+        if (__builtin_expect(__ballot(far) != 0, 0)) {
+            if (far && !occ) {
+                occ = world_any<1>(geo_all, n_pad, r, t_min, t_max);
+                pr.tests(n_pad);
+            }
+        }
+        f2 inv_x, inv_y, inv_z, noi_x, noi_y, noi_z;
+        inv_x.x = ix; inv_y.x = iy; inv_z.x = iz;
+        noi_x.x = -(ox * ix); noi_y.x = -(oy * iy); noi_z.x = -(oz * iz);
+        float lower = (float)t_min;
+        lower = lower - __builtin_fabsf(lower) * 0x1p-20f - 1e-30f;
+        // what run_f64's `upper` starts as, and here it stays: f32(t_max) (1 + 2^-20)
+        float upper = (float)t_max;
+        upper = upper + __builtin_fabsf(upper) * 0x1p-20f;
+        StackT* top = stack;
+        int32_t cur = far || occ ? kEnd : 0;  // root
+        while (cur != kEnd) {
+            descend(cur, top, ax, ay, az, inv_x, inv_y, inv_z, noi_x, noi_y, noi_z, lower, upper, pr);
+            if (cur != kEnd && !leaf_ok(cur)) cur = kEnd;
+            if (cur != kEnd) {
+                pr.leaf_iter();
+                const BvhLeaf* lf = (const BvhLeaf*)((const char*)leaves + (uint32_t)(~cur));
+                double h[kLeafBvh], disc[kLeafBvh];
+#pragma unroll
+                for (int u = 0; u < kLeafBvh; ++u) {
+                    const LeafGeo s = lf->g[u];
+                    const double ocx = s.cx - r.orig.x;
+                    const double ocy = s.cy - r.orig.y;
+                    const double ocz = s.cz - r.orig.z;
+                    h[u] = (r.dir.x * ocx + r.dir.y * ocy) + r.dir.z * ocz;
+                    const double c = ((ocx * ocx + ocy * ocy) + ocz * ocz) - s.r2;
+                    disc[u] = h[u] * h[u] - a * c;
+                }
+                // run_f64's rounds, nearest-looking slot first; a lane accepted in round 1 skips round 2.
+                // Only lanes with occ == false are here.
+                if constexpr (kLeafBvh == 2) {
+                    const bool v0 = disc[0] >= 0 && !lfilt.behind(h[0], disc[0]);
+                    const bool v1 = disc[1] >= 0 && !lfilt.behind(h[1], disc[1]);
+                    const bool p1 = v1 && (!v0 || h[1] < h[0]);  // round 1 takes slot 1
+                    if (v0 || v1) occ = accepted<-2>(p1 ? h[1] : h[0], p1 ? disc[1] : disc[0], ad, t_min, t_max, pr);
+                    if (v0 && v1 && !occ) occ = accepted<-2>(p1 ? h[0] : h[1], p1 ? disc[0] : disc[1], ad, t_min, t_max, pr);
+                } else {
+#pragma unroll
+                    for (int u = 0; u < kLeafBvh; ++u) {
+                        if (!occ && disc[u] >= 0 && !lfilt.behind(h[u], disc[u]))
+                            occ = accepted<-2>(h[u], disc[u], ad, t_min, t_max, pr);
+                    }
+                }
+                pr.tests(kLeafBvh);
+                const int32_t popped = *top;  // pop (entry 0: kEnd)
+                top -= kStride;
+                cur = occ ? kEnd : popped;
+            }
+        }
+        return occ;
     }
 };
 
@@ -2435,6 +2616,113 @@ __global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) 
                      }, geo_g, mat_g, ta, (double)b.origin_bound);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Occlusion queries (rt_occluded_rays, rt_kernel.h OcclusionArgs): one boolean per
+// caller-supplied ray — does HittableList.hit return true? — through the walkers' any-hit mode.
+// trace_loop's tiling and routing: one lane per ray, a wave per tile of 64 consecutive rays; a lane
+// whose ray (after the subtraction in targets mode) fails trace_tree_ok hands the walker the dummy
+// ray and takes the early-exit list scan behind a wave-uniform ballot.  Per tile the wave's ballot
+// of occluded live lanes is the mask word (bits past the last ray are 0), stored whole by lane 0.
+// ------------------------------------------------------------------------------------------------
+template <bool kTree, class Walker>
+__device__ __forceinline__ void occlusion_loop(const KernelParams& p, const Walker& walk,
+                                               const GeoRec* __restrict__ geo_orig, const OcclusionArgs& oa,
+                                               double origin_bound) {
+    const uint32_t lane = lane_id();
+    const uint32_t waves = gridDim.x * (blockDim.x / 64);
+    const size_t stride = oa.ray_stride;
+    Prof<0> pr;
+    uint32_t n_rays = 0, n_scan = 0, n_occ = 0;  // this wave's counts (wave-uniform)
+    for (uint32_t tile = (threadIdx.x / 64) * gridDim.x + blockIdx.x; tile < oa.n_tiles; tile += waves) {
+        // the last tile's lanes past the last ray trace that ray again and store nothing
+        const uint32_t q0 = tile * 64 + lane;
+        const bool live = q0 < oa.n_rays;
+        const size_t q = live ? q0 : oa.n_rays - 1;
+        Ray r;
+        r.orig = mk(oa.origins[q * stride], oa.origins[q * stride + 1], oa.origins[q * stride + 2]);
+        const v3 e = mk(oa.ends[q * stride], oa.ends[q * stride + 1], oa.ends[q * stride + 2]);
+        r.dir = oa.targets ? e - r.orig : e;
+        double t_min = oa.t_min, t_max = oa.t_max;
+        if (oa.intervals) {
+            t_min = oa.intervals[2 * q];
+            t_max = oa.intervals[2 * q + 1];
+        }
+        bool occ;
+        bool scan = true;
+        if constexpr (kTree) {
+            const double o3[3] = {r.orig.x, r.orig.y, r.orig.z}, d3[3] = {r.dir.x, r.dir.y, r.dir.z};
+            const bool ok = trace_tree_ok(o3, d3, t_min, t_max, origin_bound);
+            scan = !ok;
+            const double nan = __builtin_nan("");
+            Ray rw;
+            rw.orig = mk(ok ? r.orig.x : nan, ok ? r.orig.y : nan, ok ? r.orig.z : nan);
+            rw.dir = mk(ok ? r.dir.x : 1.0, ok ? r.dir.y : 0.0, ok ? r.dir.z : 0.0);
+            occ = walk.any_hit(rw, ok ? t_min : 1.0, ok ? t_max : -1.0, pr);
+            if (__ballot(scan) != 0) {
+                if (scan) occ = world_any<1>(geo_orig, p.n_pad, r, t_min, t_max);
+            }
+        } else {
+            occ = walk.any_hit(r, t_min, t_max, pr);
+        }
+        const uint64_t m = __ballot(live && occ);
+        if (live && oa.occluded) oa.occluded[q] = occ ? 1 : 0;
+        if (oa.mask && lane == 0) oa.mask[(size_t)tile] = m;  // lane 0 of a tile is always live
+        n_rays += (uint32_t)__popcll(__ballot(live));
+        n_scan += (uint32_t)__popcll(__ballot(live && scan));
+        n_occ += (uint32_t)__popcll(m);
+    }
+    // {rays, rays resolved by the list scan, occluded rays}: one vector atomic per wave and word
+    if (oa.stats && lane == 0 && n_rays) {
+        atomicAdd(oa.stats, (unsigned long long)n_rays);
+        if (n_scan) atomicAdd(oa.stats + 1, (unsigned long long)n_scan);
+        if (n_occ) atomicAdd(oa.stats + 2, (unsigned long long)n_occ);
+    }
+}
+
+// The list walk, as trace_kernel.
+template <bool kLds>
+__global__ __launch_bounds__(kBlock) void occlusion_kernel(KernelParams p, const GeoRec* __restrict__ geo_g,
+                                                           OcclusionArgs oa) {
+    extern __shared__ GeoRec lds_geo[];
+    const GeoRec* geo = geo_g;
+    if constexpr (kLds) {
+        for (uint32_t k = threadIdx.x; k < p.n_pad; k += blockDim.x) lds_geo[k] = geo_g[k];
+        __syncthreads();
+        geo = lds_geo;
+    }
+    occlusion_loop<false>(p, LinearWalker<4>{geo, p.n_pad, p.n_spheres}, geo_g, oa, 0.0);
+}
+
+// The BVH walk, the tree staged as trace_kernel_bvh stages it.  KernelParams and BvhArgs are the first
+// two arguments: the walker reads the always-list from the kernarg segment at their offsets.
+template <bool kLdsScene>
+__global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) void occlusion_kernel_bvh(
+    KernelParams p, BvhArgs b, const GeoRec* __restrict__ geo_g, OcclusionArgs oa) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const size_t scene_bytes = kLdsScene ? (size_t)bvh_leaves_offset(b.n_nodes) + (size_t)b.n_leaves * sizeof(BvhLeaf) : 0;
+    using Stack = std::conditional_t<kLdsScene, StackEntry, int32_t>;
+    using Walker = BvhWalker<kLdsScene, kBlockBvh, Stack, false>;
+    Stack* stack = (Stack*)(lds_raw + scene_bytes);
+    stack[threadIdx.x] = (Stack)Walker::kEnd;  // entry 0 of this lane's stack: popping it ends the walk
+    const BvhNode* nodes = b.nodes;
+    const BvhLeaf* leaves = b.leaves;
+    if constexpr (kLdsScene) {
+        BvhNode* ln = (BvhNode*)lds_raw;
+        BvhLeaf* ll = (BvhLeaf*)(lds_raw + bvh_leaves_offset(b.n_nodes));
+        for (uint32_t k = threadIdx.x; k < b.n_nodes; k += blockDim.x) ln[k] = b.nodes[k];
+        for (uint32_t k = threadIdx.x; k < b.n_leaves; k += blockDim.x) ll[k] = b.leaves[k];
+        __syncthreads();
+        nodes = ln;
+        leaves = ll;
+    }
+    occlusion_loop<true>(p, Walker{nodes, leaves, b.always_geo, b.always_sid, b.n_always, stack + threadIdx.x, b.origin_bound,
+                                   geo_g, p.n_pad
+#if RTZIG_BOUNDS
+                                   , b.n_nodes * (uint32_t)sizeof(BvhNode), (uint32_t)(b.n_leaves * sizeof(BvhLeaf)), b.stack_depth, oa.ctr
+#endif
+                         }, geo_g, oa, (double)b.origin_bound);
+}
+
 // Direct mode's second pass (rt_kernel.h "Work units"): thread q adds pixel q's stored colors in
 // sample order — pixelColor += rayColor(ray), camera.zig:133-136, from pixelColor = 0 — then
 // scales (:137) and writes linear f64 or the fused Color.toRgb bytes.  A wave's loads of one sample
@@ -3031,6 +3319,52 @@ extern "C" hipError_t rtk_launch_trace(const rtk::KernelParams* p, const rtk::Bv
         return hipGetLastError();
     };
     return lds_scene ? launch(trace_kernel_bvh<true>, "bvh_lds(trace)") : launch(trace_kernel_bvh<false>, "bvh_global(trace)");
+}
+
+// Occlusion queries: rtk_launch_trace's choice of structure, LDS plan and grid, for the occlusion kernels.
+extern "C" hipError_t rtk_launch_occlusion(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                           const rtk::OcclusionArgs* oa, hipStream_t stream, const char** name) {
+    using namespace rtk;
+    if (oa->n_rays == 0) return hipSuccess;
+    if (oa->ray_stride < 3 || !oa->origins || !oa->ends) return hipErrorInvalidValue;
+    OcclusionArgs a = *oa;
+    a.n_tiles = (uint32_t)(((uint64_t)a.n_rays + 63) / 64);
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+        cus = 256;
+    // blocks: a wave per tile, at least one block per CU while tiles last, at most the resident grid
+    auto grid_of = [&](uint32_t block, uint64_t cap) {
+        const uint64_t need = ((uint64_t)a.n_tiles + block / 64 - 1) / (block / 64);
+        const uint64_t spread = a.n_tiles < (uint32_t)cus ? a.n_tiles : (uint64_t)cus;
+        const uint64_t g = need > spread ? need : spread;
+        return (uint32_t)(g < cap ? g : cap);
+    };
+    if (b == nullptr) {
+        const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
+        const size_t shmem = list_walk_lds(v.lds, p->n_pad, false);  // no seed window
+        auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+            const uint64_t cap = persistent_blocks(kernel, shmem);
+            if (name) *name = nm;
+            hipLaunchKernelGGL(kernel, dim3(grid_of(kBlock, cap)), dim3(kBlock), shmem, stream, *p, geo, a);
+            return hipGetLastError();
+        };
+        return v.lds ? launch(occlusion_kernel<true>, "lds_u4(occlusion)") : launch(occlusion_kernel<false>, "smem_u4(occlusion)");
+    }
+    if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
+    const uint32_t block = (uint32_t)kBlockBvh;
+    const auto [lds_scene, scene_bytes, stack_bytes] = bvh_lds_plan(b->n_nodes, b->n_leaves, b->stack_depth, block, kLdsSceneBudget);
+    const size_t shmem = (lds_scene ? scene_bytes : 0) + stack_bytes;
+    auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+        uint32_t cap32 = 0;
+        const hipError_t ea = rtk_resident_blocks((const void*)kernel, (int)block, shmem, &cap32);
+        if (ea != hipSuccess) return ea;
+        if (name) *name = nm;
+        hipLaunchKernelGGL(kernel, dim3(grid_of(block, cap32)), dim3(block), shmem, stream, *p, *b, geo, a);
+        return hipGetLastError();
+    };
+    return lds_scene ? launch(occlusion_kernel_bvh<true>, "bvh_lds(occlusion)")
+                     : launch(occlusion_kernel_bvh<false>, "bvh_global(occlusion)");
 }
 
 extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, hipStream_t stream) {

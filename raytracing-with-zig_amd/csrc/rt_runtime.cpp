@@ -1084,6 +1084,55 @@ int rt_trace_rays(rt_context* ctx, const void* d_origins, const void* d_directio
     return close_call(ctx, s, ev);
 }
 
+// ---- occlusion queries (rt.h) ------------------------------------------------------
+// rt_trace_rays' launch with the occlusion kernel in place of the trace kernel; its checks in its
+// order and words (rt_trace_rays' own sit between its `out` check and stay where they are).
+int rt_occluded_rays(rt_context* ctx, const void* d_origins, const void* d_ends, uint32_t ray_stride, uint64_t n_rays,
+                     double t_min, double t_max, const void* d_intervals, uint32_t flags, uint8_t* d_occluded,
+                     uint64_t* d_mask, void* d_stats, void* stream) {
+    if (!d_origins) { rt_set_last_error("null d_origins"); return RT_ERR_INVALID; }
+    if (!d_ends) { rt_set_last_error("null d_ends"); return RT_ERR_INVALID; }
+    if (ray_stride == 1 || ray_stride == 2) { rt_set_last_error("ray_stride must be 0 or at least 3"); return RT_ERR_INVALID; }
+    if (n_rays >= (1ull << 32)) { rt_set_last_error("n_rays must be below 2^32"); return RT_ERR_INVALID; }
+    if (flags & ~RT_OCCLUSION_TARGETS) { rt_set_last_error("flags: unknown bits (RT_OCCLUSION_TARGETS is the only flag)"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (n_rays == 0) return RT_OK;
+    if (!d_occluded && !d_mask && !d_stats) return RT_OK;  // no launch
+    if (ctx->n_spheres == 0) { rt_set_last_error("no scene uploaded"); return RT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    if (!rc) rc = ensure_counters(ctx, s);
+    if (rc) return rc;
+    const bool bvh = use_bvh(ctx);
+    rtk::KernelParams p;
+    std::memset(&p, 0, sizeof p);
+    p.n_spheres = ctx->n_spheres;
+    p.n_pad = (ctx->n_spheres + rtk::kPad - 1) / rtk::kPad * rtk::kPad;
+    rtk::OcclusionArgs oa{};
+    oa.origins = (const double*)d_origins;
+    oa.ends = (const double*)d_ends;
+    oa.intervals = (const double*)d_intervals;
+    oa.occluded = d_occluded;
+    oa.mask = (unsigned long long*)d_mask;
+    oa.stats = (unsigned long long*)d_stats;
+    oa.ctr = ctx->d_ctr;
+    oa.t_min = t_min;
+    oa.t_max = t_max;
+    oa.n_rays = (uint32_t)n_rays;
+    oa.ray_stride = ray_stride ? ray_stride : 3;
+    oa.targets = flags & RT_OCCLUSION_TARGETS;
+    hipEvent_t* ev = nullptr;
+    rc = open_call(ctx, s, 1, &ev);
+    if (rc) return rc;
+    if (ev) {
+        HIP_CHECK(hipEventRecord(ev[0], s));
+        ctx->no_reduce[ctx->call_first] = 1;  // no reduce pass: reduce_ms is 0, not the gap between two events
+    }
+    HIP_CHECK(rtk_launch_occlusion(&p, bvh ? &ctx->bvh : nullptr, ctx->d_geo, &oa, s, &ctx->last_kernel));
+    return close_call(ctx, s, ev);
+}
+
 int rt_context_origin_bound(rt_context* ctx, double* bound) {
     if (!ctx || !bound) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
     // the bound the kernels compare with: the builder's, rounded down to f32 (upload_bvh)

@@ -70,6 +70,15 @@ class Scene:
         return trace_rays(self.world, origins, directions, t_min=t_min, t_max=t_max, intervals=intervals,
                           device=device)
 
+    def occluded(self, origins, ends, t_min=1e-3, t_max=INF, intervals=None, targets=False, device=0):
+        """Does world.hit return true?  One bool per ray, on the GPU (rtzig.occluded)."""
+        return occluded(self.world, origins, ends, t_min=t_min, t_max=t_max, intervals=intervals, targets=targets,
+                        device=device)
+
+    def visible(self, a, b, eps=1e-3, device=0):
+        """Line of sight: no sphere has a root in the open segment (eps, 1) from a[q] to b[q]."""
+        return ~occluded(self.world, a, b, t_min=eps, t_max=1.0, targets=True, device=device)
+
 
 def _concat(a, b):
     out = (RtSphere * (len(a) + len(b)))()
@@ -430,6 +439,48 @@ def trace_rays(spheres, origins, directions, t_min=1e-3, t_max=INF, intervals=No
     return res
 
 
+def occluded(spheres, origins, ends, t_min=1e-3, t_max=INF, intervals=None, targets=False, device=0):
+    """Occlusion of caller-supplied rays on one GPU (rt_occluded_rays): (n,) bool, True where
+    HittableList.hit returns true in the reference's f64 arithmetic — trace_rays' index >= 0, from a walk
+    that stops at the first accepted root.  origins, ends: (n, 3) arrays; `ends` holds directions, or
+    with targets=True end points (the direction is end - origin, and (eps, 1.0) is the open segment);
+    intervals: None or (n, 2), per-ray (t_min, t_max)."""
+    import torch
+
+    o = np.ascontiguousarray(origins, np.float64)
+    e = np.ascontiguousarray(ends, np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or e.shape != o.shape:
+        raise ValueError("origins and ends must both be (n, 3)")
+    n = o.shape[0]
+    iv = None
+    if intervals is not None:
+        iv = np.ascontiguousarray(intervals, np.float64)
+        if iv.shape != (n, 2):
+            raise ValueError("intervals must be (n, 2)")
+    if n == 0:
+        return np.zeros(0, bool)
+    ns = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * ns)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_o = torch.from_numpy(o).to(dev)
+            d_e = torch.from_numpy(e).to(dev)
+            d_iv = torch.from_numpy(iv).to(dev) if iv is not None else None
+            occ = torch.empty(n, dtype=torch.uint8, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            r.occluded_rays(d_o.data_ptr(), d_e.data_ptr(), n, t_min, t_max, d_occluded_ptr=occ.data_ptr(),
+                            d_intervals_ptr=d_iv.data_ptr() if d_iv is not None else None, targets=targets,
+                            stream_ptr=stream)
+            res = occ.cpu().numpy().astype(bool)  # waits for the stream
+            r.sync()  # reports a failure the kernel recorded
+    finally:
+        r.close()
+    return res
+
+
 def denoise_params(**overrides):
     """rt_denoise_params: the library's defaults (rt_denoise_default_params: levels 2, sigma_l 4,
     sigma_n 32, sigma_a 32, sigma_z 0.05, sigma_h 4, epsilon 1e-6) with the given fields replaced."""
@@ -717,6 +768,21 @@ class DeviceRenderer:
               self.lib.rt_trace_rays(self.ctx, C.c_void_p(d_origins_ptr or 0), C.c_void_p(d_directions_ptr or 0),
                                      ray_stride, n_rays, t_min, t_max, C.c_void_p(d_intervals_ptr or 0),
                                      C.byref(hits), C.c_void_p(d_stats_ptr or 0), C.c_void_p(stream_ptr or 0)))
+
+    def occluded_rays(self, d_origins_ptr, d_ends_ptr, n_rays, t_min=1e-3, t_max=INF, d_occluded_ptr=None,
+                      d_mask_ptr=None, d_intervals_ptr=None, d_stats_ptr=None, ray_stride=3, targets=False,
+                      stream_ptr=None):
+        """rt_occluded_rays: is ray q occluded (HittableList.hit true), for n_rays rays on the device.
+        Rays and intervals as trace_rays; with targets=True d_ends_ptr holds end points and the direction
+        is end - origin.  Outputs, each skipped when None: occluded (n u8, 1 / 0), mask (ceil(n / 64) u64,
+        bit q & 63 of word q >> 6).  d_stats_ptr: 3 x u64, incremented by {rays, rays answered by the list
+        scan, occluded rays}.  Always parity arithmetic."""
+        check("rt_occluded_rays",
+              self.lib.rt_occluded_rays(self.ctx, C.c_void_p(d_origins_ptr or 0), C.c_void_p(d_ends_ptr or 0),
+                                        ray_stride, n_rays, t_min, t_max, C.c_void_p(d_intervals_ptr or 0),
+                                        abi.OCCLUSION_TARGETS if targets else 0, C.c_void_p(d_occluded_ptr or 0),
+                                        C.c_void_p(d_mask_ptr or 0), C.c_void_p(d_stats_ptr or 0),
+                                        C.c_void_p(stream_ptr or 0)))
 
     def origin_bound(self):
         """rt_context_origin_bound: rays starting within it (max |o_k|) may use the tree; 0: the list walk."""

@@ -32,6 +32,7 @@ EXPORTED = [
     "rt_temporal_default_params",
     "rt_temporal_accumulate",
     "rt_trace_rays",
+    "rt_occluded_rays",
     "rt_context_origin_bound",
     "rt_context_reserve_origin_bound",
     "rt_context_flush",
@@ -102,6 +103,8 @@ def _declare(lib):
                                              P(RtTemporalParams), vp, vp]),
         "rt_trace_rays": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_double, C.c_double, vp, P(RtRayHits),
                                     vp, vp]),
+        "rt_occluded_rays": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_double, C.c_double, vp, C.c_uint32,
+                                       vp, vp, vp, vp]),
         "rt_context_origin_bound": (C.c_int, [vp, P(C.c_double)]),
         "rt_context_reserve_origin_bound": (C.c_int, [vp, C.c_double]),
         "rt_context_flush": (C.c_int, [vp]),

@@ -35,6 +35,10 @@
 #              pass at 16 samples plus a copy of the bytes it moves, and the incoherent, far-origin and
 #              tiny-batch figures (tools/trace_cost.py; its JSON on stdout is kept as
 #              profiles/trace/cost.json).  Its GPU tests (tests/test_gpu_trace.py) run with the `tests` step
+#   occlusion  what an occlusion query costs against the closest-hit query on the same rays: primary
+#              visibility, shadow rays and segments to a point light (tools/occlusion_cost.py; its JSON on
+#              stdout is kept as profiles/occlusion/cost.json).  Its GPU tests (tests/test_gpu_occlusion.py)
+#              run with the `tests` step
 #   denoise   what rt_denoise costs against the 16-sample gather pass it stands in for, per level and
 #              kernel form, and the RMSE table against a 500-spp frame, on config 4's image
 #              (tools/denoise_cost.py; the "cost" and "quality" objects of its JSON on stdout are kept
@@ -82,6 +86,7 @@ for step in "$@"; do
     adaptive) run adaptive 300 python3 -u tools/adaptive_cost.py ;;
     features) run features 200 python3 -u tools/feature_cost.py ;;
     trace)   run trace 300 python3 -u tools/trace_cost.py ;;
+    occlusion) run occlusion 300 python3 -u tools/occlusion_cost.py ;;
     denoise) run denoise 300 python3 -u tools/denoise_cost.py ;;
     temporal) run temporal 300 python3 -u tools/temporal_cost.py ;;
     peak)    run peak 300 ./tools/bin/peak_rates ${PEAK_MS:-60} ${PEAK_MODE:-2} ;;
