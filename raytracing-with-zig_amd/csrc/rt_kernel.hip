@@ -68,6 +68,7 @@
 #include "rt_device.h"
 #include "rt_kernel.h"
 #include "rt_leaf_filter.h"
+#include "rt_slab.h"
 #include "rt_units.h"
 
 #pragma clang fp contract(off)
@@ -531,47 +532,7 @@ struct LinearWalker {
     }
 };
 
-// Slab-interval ends: max(x, y, z, lower) and min(x, y, z, upper) as hardware v_max3/v_min3 +
-// v_max/v_min.  With IEEE mode on (the default) these return the non-NaN operand for quiet NaNs —
-// exactly fmaxf/fminf on every value this walk produces (arithmetic never yields signaling NaNs) —
-// but written as builtins the compiler re-canonicalizes the loop-carried bounds every iteration.
-#ifndef RTZIG_WALK_FORM
-#define RTZIG_WALK_FORM 0
-#endif
-#if RTZIG_WALK_FORM == 4
-__device__ __forceinline__ float slab_near(float x, float y, float z, float lower) {
-    float t, r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(t) : "v"(z), "v"(lower));
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(t));
-    return r;
-}
-__device__ __forceinline__ float slab_far(float x, float y, float z, float upper) {
-    float t, r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(t) : "v"(z), "v"(upper));
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(t));
-    return r;
-}
-#elif RTZIG_WALK_FORM >= 1
-__device__ __forceinline__ float slab_near(float x, float y, float z, float lower) {
-    return __builtin_fmaxf(__builtin_fmaxf(x, y), __builtin_fmaxf(z, lower));
-}
-__device__ __forceinline__ float slab_far(float x, float y, float z, float upper) {
-    return __builtin_fminf(__builtin_fminf(x, y), __builtin_fminf(z, upper));
-}
-#else
-__device__ __forceinline__ float slab_near(float x, float y, float z, float lower) {
-    float t, r;
-    asm volatile("v_max_f32 %0, %1, %2" : "=v"(t) : "v"(z), "v"(lower));
-    asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(t));
-    return r;
-}
-__device__ __forceinline__ float slab_far(float x, float y, float z, float upper) {
-    float t, r;
-    asm volatile("v_min_f32 %0, %1, %2" : "=v"(t) : "v"(z), "v"(upper));
-    asm volatile("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(y), "v"(t));
-    return r;
-}
-#endif
+// slab_near / slab_far, pk_fma_lo (with the RTZIG_WALK_FORM knob) and rcp_clamp: rt_slab.h
 
 // v_cndmask_b32 on a wave mask held in SGPRs: lanes whose bit of `m` is set get `t`, others `f`
 __device__ __forceinline__ int32_t sel_mask(int32_t f, int32_t t, uint64_t m) {
@@ -613,28 +574,6 @@ constexpr bool kDrainTrips = RTZIG_DRAIN == 1;    // drained trips are not cappe
 #endif
 constexpr int kRefillMin = RTZIG_REFILL_MIN;
 constexpr int kSuspended = -2;
-typedef float f2 __attribute__((ext_vector_type(2)));
-// {b.x * m.x + a.x, b.y * m.x + a.x}: v_pk_fma_f32 with the second and third operands' low halves
-// broadcast to the high lane (op_sel_hi:[1,0,0]); their high halves are never read
-// Forms of the inner step (A/B knob): 0 the shipped one (inline-asm v_pk_fma_f32 with a
-// broadcast operand, volatile-asm v_max3/v_min3, asm ds_read_b64); 1 builtin packed fma and
-// min/max; 2 form 1 with plain LDS loads (ds_read2_b64); 4 form 0 with the slab min/max as
-// non-volatile asm (schedulable); 5 form 0 with builtin min/max.
-#if RTZIG_WALK_FORM == 4 || RTZIG_WALK_FORM == 5
-#define RTK_PK_ASM 1
-#else
-#define RTK_PK_ASM (RTZIG_WALK_FORM == 0)
-#endif
-__device__ __forceinline__ f2 pk_fma_lo(f2 b, f2 m, f2 a) {
-#if !RTK_PK_ASM
-    const f2 mm = {m.x, m.x}, aa = {a.x, a.x};
-    return __builtin_elementwise_fma(b, mm, aa);
-#else
-    f2 r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(b), "v"(m), "v"(a));
-    return r;
-#endif
-}
 typedef int32_t i2 __attribute__((ext_vector_type(2)));
 
 // LDS reads issued as single instructions (the caller waits with s_waitcnt lgkmcnt(0), naming the
@@ -994,9 +933,9 @@ struct BvhWalker {
             pr.tests(n_always);
         }
         const float ox = r.orig.x, oy = r.orig.y, oz = r.orig.z;
-        const float ix = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(r.dir.x), -1e30f, 1e30f);
-        const float iy = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(r.dir.y), -1e30f, 1e30f);
-        const float iz = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(r.dir.z), -1e30f, 1e30f);
+        const float ix = rcp_clamp(r.dir.x);
+        const float iy = rcp_clamp(r.dir.y);
+        const float iz = rcp_clamp(r.dir.z);
         const uint32_t ax = ix < 0 ? 8u : 0u, ay = 16u + (iy < 0 ? 8u : 0u), az = 32u + (iz < 0 ? 8u : 0u);
         // origins beyond the boxes' origin bound walk the whole list (exact f64 scan, as in parity mode)
         const bool far = !(kSusp && resume) &&
@@ -1117,18 +1056,19 @@ struct BvhWalker {
         // v_rcp_f32 (1 ulp) instead of three correctly rounded f32 divisions (~11 ops each), then
         // clamped to +-1e30 by one v_med3 per axis: the inverse of a component clamped to
         // +-1e-30 (rcp(+-0) = +-inf keeps its sign), one op instead of compare + copysign + select
-        const float ix = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dx), -1e30f, 1e30f);
-        const float iy = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dy), -1e30f, 1e30f);
-        const float iz = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dz), -1e30f, 1e30f);
+        const float ix = rcp_clamp(dx);
+        const float iy = rcp_clamp(dy);
+        const float iz = rcp_clamp(dz);
         // slab planes as t = fma(bound, inv, -o*inv): one op per plane.  Error (position space,
         // per axis) <= 2^-24 (4|bound| + 5|o|), inside the padding of rt_bvh.cpp.  fma is monotone
         // in `bound`, so for inv > 0 the lo plane is the near one and for inv < 0 the hi plane: the
         // lane reads its (near, far) pair per axis at byte +0 or +8 of the axis's {lo, hi, hi, lo}
         // (rtk::BvhNode) and both planes of an axis come out of one packed fma.  inv is finite, and
         // nonzero unless the f32 component overflowed (then every point of the ray past t_min lies
-        // beyond any boundable box, and the [0, 0] slab culls it correctly), and NaN only for a NaN
-        // direction (whose f64 sphere tests never pass), so the pick matches the min/max of the
-        // two planes exactly; an
+        // beyond any boundable box, and the [0, 0] slab culls it correctly), and never NaN: for a NaN
+        // component v_med3 returns the least of its operands, -1e30 (probed: tests/test_gpu_primitives.py),
+        // an ordinary clamped axis of a direction whose f64 sphere tests never pass; so the pick
+        // matches the min/max of the two planes exactly; an
         // overflowed plane is +-inf in ray order, and NaN arises only from a NaN origin, which
         // v_max3/v_min3 drop (the box is kept: permissive, never a wrong cull).
         const uint32_t ax = ix < 0 ? 8u : 0u, ay = 16u + (iy < 0 ? 8u : 0u), az = 32u + (iz < 0 ? 8u : 0u);
@@ -1354,9 +1294,9 @@ struct BvhWalker {
         // the f32 ray, the slab constants and the far-origin rule: run_f64's, which see
         const float ox = (float)r.orig.x, oy = (float)r.orig.y, oz = (float)r.orig.z;
         const float dx = (float)r.dir.x, dy = (float)r.dir.y, dz = (float)r.dir.z;
-        const float ix = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dx), -1e30f, 1e30f);
-        const float iy = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dy), -1e30f, 1e30f);
-        const float iz = __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(dz), -1e30f, 1e30f);
+        const float ix = rcp_clamp(dx);
+        const float iy = rcp_clamp(dy);
+        const float iz = rcp_clamp(dz);
         const uint32_t ax = ix < 0 ? 8u : 0u, ay = 16u + (iy < 0 ? 8u : 0u), az = 32u + (iz < 0 ? 8u : 0u);
         const bool far = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ox), __builtin_fabsf(oy)), __builtin_fabsf(oz)) >
                          origin_bound;

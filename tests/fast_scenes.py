@@ -6,14 +6,16 @@ tests/test_fast_oracle.py (GPU: the f32 fast mode against the same pair).  Every
 
 Also the scene and parameter builders that more than one test file uses: always_list_scene and
 far_origin_scene (tests/test_gpu_parity.py, tests/test_gpu_domain.py) and golden_params, the golden
-test's camera preset (tests/test_oracle.py, tests/test_host.py, tests/test_gpu_parity.py).
+test's camera preset (tests/test_oracle.py, tests/test_host.py, tests/test_gpu_parity.py); lattice and
+skim_camera, the scene and the camera of the slab-certificate tests (tests/test_slab_inputs.py,
+tests/test_gpu_slab.py).
 """
 import math
 
 import numpy as np
 
 import rtzig
-from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtCameraParams, RtSphere
+from rtzig.abi import D3, RT_DIELECTRIC, RT_LAMBERTIAN, RT_METAL, RtCamera, RtCameraParams, RtSphere
 
 INF = math.inf
 THETAS = (1e-3, 1e-4, 1e-5)
@@ -134,6 +136,44 @@ def far_origin_scene(width=96):
     cam = (rtzig.Camera.builder(width, 1.5).setScene(scene).setDefocusAngle(0.6).setFocusDist(10)
            .setViewport((13, 2, 3), (0, 0, 0), 20).setSamplesPerPixel(4).build())
     return arr, cam
+
+
+def lattice(T=0):
+    """The scene of the slab-certificate tests (tests/slab_support.py): a 4 x 4 x 4 lattice of radius-0.25
+    spheres at unit spacing, translated by (T, T / 2, -T).  Equal spheres: none is big against the
+    median, so none goes to the always-list, and the poles of a layer share one plane, which is a face
+    of every box on the way.  Materials by index: lambertian, metal, dielectric in turn."""
+    sph = []
+    for i in range(4):
+        for j in range(4):
+            for k in range(4):
+                n = len(sph)
+                sph.append(RtSphere(center=D3(i + T, j + T / 2, k - T), radius=0.25, material=(RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC)[n % 3],
+                                    albedo=D3(0.3 + 0.1 * i, 0.3 + 0.1 * j, 0.3 + 0.1 * k), fuzz=0.1 * (n % 4),
+                                    refraction_index=1.5))
+    scene = rtzig.Scene.init(0x1A77 + T)
+    scene.world = (RtSphere * len(sph))(*sph)
+    return scene
+
+
+def skim_camera(T, dv_y, spp=8, bounce_max=4):
+    """A 64 x 4 camera on lattice(T) whose every primary ray skims: it sits 0.3 f32 ulps under the plane
+    of the top poles of layer 1 (its f32 origin rounds onto the plane: what is left of the slab on that
+    axis is the rounding of o * inv), before row (., 1, 1), and looks along +x.  du spreads the 64 columns over
+    two thirds of the width of the cap that lies above that height; dv = (0, dv_y, 0), so the rows differ
+    in a tilt of that size alone (d_y = dv_y (j + U(-0.5, 0.5)): both signs in row 0; 0 exactly for
+    dv_y = 0).  The fields are set directly: no builder produces a dv of 2^-30."""
+    scene = lattice(T)
+    plane = 1.25 + T / 2
+    delta = 0.3 * float(np.spacing(np.float32(plane)))
+    du_z = math.sqrt(2 * 0.25 * delta) / 96  # the pixels are 1 away, the pole 2
+    center = (T - 2.0, plane - delta, 1.0 - T)
+    cam = RtCamera(image_width=64, image_height=4, samples_per_pixel=spp, bounce_max=bounce_max,
+                   pixel_samples_scale=1.0 / spp, center=D3(*center),
+                   pixel0=D3(center[0] + 1.0, center[1], center[2] - 31.5 * du_z), du=D3(0, 0, du_z), dv=D3(0, dv_y, 0),
+                   defocus_disk_u=D3(0, 0, 0), defocus_disk_v=D3(0, 0, 0), defocus_angle=0.0, t_min=1e-3, t_max=INF,
+                   seed=scene.seed)
+    return rtzig.Camera(cam, scene)
 
 
 def golden_params(width=400, aspect=16.0 / 9.0, spp=10, seed=0xDEADBEEF):

@@ -1,5 +1,5 @@
-// rt_probe.hip — the path tracer's f64 primitives (csrc/rt_device.h, csrc/rt_leaf_filter.h), one small
-// kernel each, so that a test can feed them operands value by value (tests/test_gpu_primitives.py).
+// rt_probe.hip — the path tracer's f64 primitives (csrc/rt_device.h, csrc/rt_leaf_filter.h) and the BVH
+// walk's f32 slab primitives (csrc/rt_slab.h), one small kernel each, so that a test can feed them operands value by value (tests/test_gpu_primitives.py).
 // Test infrastructure like the oracle: built as raytracing-with-zig_amd/librtzig_probe.so with the
 // kernels' own flags, never linked into the product.
 //
@@ -7,7 +7,8 @@
 // of n 8-byte elements: input plane p of element i at in[p * n + i], output plane likewise (the leaf
 // filter's output is one plane of n bytes).  n is a multiple of 256: kernels run whole blocks of 256
 // threads with every lane active (RayDiv, sqrt_g, unit and Random.float take wave-wide ballots), and
-// the caller pads.  k is the number of RNG steps per element (RNG ops only, at most kMaxDraws = 64).
+// the caller pads.  An f32 operand or result is the low half of its 8-byte element (the high half of a
+// result is 0).  k is the number of RNG steps per element (RNG ops only, at most kMaxDraws = 64).
 // Every kernel reads and writes planes of its own element index only, and the entry point refuses
 // buffers smaller than the op's planes.
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 
 #include "../../raytracing-with-zig_amd/csrc/rt_device.h"
 #include "../../raytracing-with-zig_amd/csrc/rt_leaf_filter.h"
+#include "../../raytracing-with-zig_amd/csrc/rt_slab.h"
 
 namespace {
 using namespace rtk;
@@ -39,7 +41,12 @@ enum Op : int {
     kStateUniformFull = 12,   // ... RngT<false>
     kLeafBehind = 13,  // a, t_min, h, disc -> LeafFilter::make(a, t_min).behind(h, disc), one byte
     kMulRcp = 14,      // a, x -> x * (1.0 / a): the control, two roundings
-    kOps = 15
+    kRcpClamp = 15,    // d -> rcp_clamp(d) (f32)
+    kPkFmaLo = 16,     // b.x, b.y, m.x, m.y, a.x, a.y -> pk_fma_lo(b, m, a).x, .y (f32)
+    kPkMulAdd = 17,    // ... -> b.x * m.x + a.x, b.y * m.x + a.x: the control, two roundings each
+    kSlabNear = 18,    // x, y, z, lower -> slab_near (f32)
+    kSlabFar = 19,     // x, y, z, upper -> slab_far (f32)
+    kOps = 20
 };
 
 struct Planes { int in, out; bool draws, bytes; };  // out planes are per draw when `draws`
@@ -56,6 +63,9 @@ __host__ constexpr Planes planes(int op) {
         case kStateWordsLean: case kStateWordsFull: case kStateUniformLean: case kStateUniformFull:
             return {5, 1, true, false};
         case kLeafBehind: return {4, 1, false, true};
+        case kRcpClamp: return {1, 1, false, false};
+        case kPkFmaLo: case kPkMulAdd: return {6, 2, false, false};
+        case kSlabNear: case kSlabFar: return {4, 1, false, false};
         default: return {0, 0, false, false};
     }
 }
@@ -151,6 +161,39 @@ __global__ __launch_bounds__(kBlock) void k_leaf_behind(const double* in, uint8_
     out[i] = f.behind(in[2 * n + i], in[3 * n + i]) ? 1 : 0;
 }
 
+// f32 operands and results: the low half of an 8-byte element
+__device__ __forceinline__ float ldf(const uint64_t* in, uint64_t n, uint64_t i, int p) {
+    return __builtin_bit_cast(float, (uint32_t)in[(uint64_t)p * n + i]);
+}
+__device__ __forceinline__ uint64_t bits_of(float x) { return (uint64_t)__builtin_bit_cast(uint32_t, x); }
+
+__global__ __launch_bounds__(kBlock) void k_rcp_clamp(const uint64_t* in, uint64_t* out, uint64_t n) {
+    const uint64_t i = gid();
+    out[i] = bits_of(rcp_clamp(ldf(in, n, i, 0)));
+}
+// the walk's call: the constants of an axis in the low halves of m and a, whose high halves are never read
+__global__ __launch_bounds__(kBlock) void k_pk_fma_lo(const uint64_t* in, uint64_t* out, uint64_t n) {
+    const uint64_t i = gid();
+    const f2 b = {ldf(in, n, i, 0), ldf(in, n, i, 1)}, m = {ldf(in, n, i, 2), ldf(in, n, i, 3)};
+    const f2 a = {ldf(in, n, i, 4), ldf(in, n, i, 5)};
+    const f2 r = pk_fma_lo(b, m, a);
+    out[i] = bits_of(r.x);
+    out[n + i] = bits_of(r.y);
+}
+__global__ __launch_bounds__(kBlock) void k_pk_mul_add(const uint64_t* in, uint64_t* out, uint64_t n) {
+    const uint64_t i = gid();
+    const float m = ldf(in, n, i, 2), a = ldf(in, n, i, 4);
+    const float px = ldf(in, n, i, 0) * m, py = ldf(in, n, i, 1) * m;  // contraction is off (rt_device.h)
+    out[i] = bits_of(px + a);
+    out[n + i] = bits_of(py + a);
+}
+template <bool kFar>
+__global__ __launch_bounds__(kBlock) void k_slab(const uint64_t* in, uint64_t* out, uint64_t n) {
+    const uint64_t i = gid();
+    const float x = ldf(in, n, i, 0), y = ldf(in, n, i, 1), z = ldf(in, n, i, 2), w = ldf(in, n, i, 3);
+    out[i] = bits_of(kFar ? slab_far(x, y, z, w) : slab_near(x, y, z, w));
+}
+
 }  // namespace
 
 extern "C" {
@@ -201,6 +244,11 @@ __attribute__((visibility("default"))) int rt_probe_run(int op, const void* in, 
         case kStateUniformFull: k_state<false, true><<<grid, block, 0, s>>>(uin, uout, n, k); break;
         case kLeafBehind: k_leaf_behind<<<grid, block, 0, s>>>(din, (uint8_t*)out, n); break;
         case kMulRcp: k_mulrcp<<<grid, block, 0, s>>>(din, dout, n); break;
+        case kRcpClamp: k_rcp_clamp<<<grid, block, 0, s>>>(uin, uout, n); break;
+        case kPkFmaLo: k_pk_fma_lo<<<grid, block, 0, s>>>(uin, uout, n); break;
+        case kPkMulAdd: k_pk_mul_add<<<grid, block, 0, s>>>(uin, uout, n); break;
+        case kSlabNear: k_slab<false><<<grid, block, 0, s>>>(uin, uout, n); break;
+        case kSlabFar: k_slab<true><<<grid, block, 0, s>>>(uin, uout, n); break;
         default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -5;

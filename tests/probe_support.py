@@ -12,6 +12,8 @@ import subprocess
 
 import numpy as np
 
+from slab_support import fma32, rcp_clamp
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "raytracing-with-zig_amd")
 PROBE_SO = os.path.join(PKG, "librtzig_probe.so")
@@ -19,7 +21,8 @@ LEAF_CPP = os.path.join(ROOT, "tests", "cpp", "test_leaf_filter.cpp")
 
 OPS = dict(sqrt=0, unit=1, unit_accepted=2, raydiv=3, reflect=4, refract=5, range_pm1=6, sample_key=7,
            seed_words=8, state_words_lean=9, state_words_full=10, state_uniform_lean=11,
-           state_uniform_full=12, leaf_behind=13, mul_rcp=14)
+           state_uniform_full=12, leaf_behind=13, mul_rcp=14, rcp_clamp=15, pk_fma_lo=16, pk_mul_add=17,
+           slab_near=18, slab_far=19)
 LANES = (0, 31, 32, 63)  # where the one special value of a wave is put
 U64 = np.uint64
 M52 = (1 << 52) - 1
@@ -637,3 +640,128 @@ def leaf_filter_cases(exe, tmp_dir, n=1 << 16):
     raw = np.fromfile(path, np.uint8)
     assert raw.size == 33 * n, f"dump of {raw.size} bytes"
     return raw[:32 * n].view(np.float64).reshape(4, n), raw[32 * n:]
+
+
+# ---- the walk's f32 slab primitives (csrc/rt_slab.h) ------------------------------------------------------------
+F32, U32 = np.float32, np.uint32
+QNAN32 = 0x7fc00000
+FLT_MIN, FLT_MAX = float(np.finfo(F32).tiny), float(np.finfo(F32).max)
+
+
+def f32_plane(x):
+    """An f32 array as a probe plane: its bits in the low halves of 8-byte elements."""
+    return np.ascontiguousarray(x, F32).view(U32).astype(U64)
+
+
+def f32_of(plane):
+    """The f32 values of an output plane (the high halves must be 0)."""
+    plane = np.asarray(plane, U64)
+    assert (plane >> U64(32) == 0).all(), "the high half of an f32 result is 0"
+    return plane.astype(U32).view(F32)
+
+
+def bits32(x):
+    return np.ascontiguousarray(x, F32).view(U32)
+
+
+def rcp_inputs(per_exponent=24, seed=501):
+    """f32 operands of rcp_clamp: every biased exponent 0..255 with random mantissas and both signs (0:
+    denormals, 255: NaNs of either sign), then the edges: +-0, the smallest and the largest denormal,
+    +-FLT_MIN, +-FLT_MAX, +-inf, the quiet NaN, and every power of two with its neighbours at +-1 ulp."""
+    rng = np.random.default_rng(seed)
+    e = np.repeat(np.arange(256, dtype=U32), per_exponent)
+    m = rng.integers(1, 1 << 23, len(e), dtype=np.int64).astype(U32)
+    sgn = rng.integers(0, 2, len(e), dtype=np.int64).astype(U32)
+    rand = (sgn << U32(31)) | (e << U32(23)) | m
+    edge = [0, 1, 0x007fffff, 0x00800000, 0x7f7fffff, 0x7f800000, QNAN32]
+    edge += [b | 0x80000000 for b in edge]
+    pow2 = np.arange(1, 255, dtype=np.int64) << 23
+    near = np.concatenate([pow2 - 1, pow2, pow2 + 1])
+    near = np.concatenate([near, near | 0x80000000])
+    return np.concatenate([rand, np.array(edge, np.int64).astype(U32), near.astype(U32)]).view(F32)
+
+
+def rcp_classes(x):
+    """(normal, tiny, inf, nan) masks of rcp_clamp's operands: `normal` are the operands whose reciprocal
+    is normal and inside the clamp with a binade to spare (2^-99 <= |x| <= 2^126), `tiny` the zeros,
+    denormals and normal operands whose reciprocal lies a quarter beyond the clamp (|x| < 2^-100: 1 / x >
+    1.26e30).  Neither: the binade where the clamp sets in, and the operands whose reciprocal is denormal."""
+    x = np.asarray(x, F32)
+    with np.errstate(invalid="ignore"):  # a signalling NaN among the operands
+        ax = np.abs(x.astype(np.float64))
+    nan = np.isnan(x)
+    inf = np.isinf(x)
+    tiny = ax < 2.0 ** -100
+    normal = ~nan & ~inf & (ax >= 2.0 ** -99) & (ax <= 2.0 ** 126)
+    return normal, tiny, inf, nan
+
+
+def rcp_ulp_error(got, x):
+    """|got - 1 / x| in ulps of the correctly rounded f32 reciprocal, for normal operands."""
+    x64 = np.asarray(x, F32).astype(np.float64)
+    want = (1.0 / x64).astype(F32)
+    return np.abs(np.asarray(got, F32).astype(np.float64) - 1.0 / x64) / np.spacing(np.abs(want)).astype(np.float64)
+
+
+def pk_fma_inputs(n=1 << 14, seed=502):
+    """(b.x, b.y, m.x, m.y, a.x, a.y) f32 planes of pk_fma_lo.  Thirds: random operands of mixed scale;
+    a.x = -fl(b.x m.x) moved by 0..3 ulps, so the x lane's sum cancels to the product's rounding residual,
+    where one rounding and two differ in every bit; the same for the y lane.  m.y and a.y, which the
+    instruction must not read, hold NaN, +-FLT_MAX and +-inf in turn."""
+    rng = np.random.default_rng(seed)
+    r = lambda lo, hi: (rng.choice([-1.0, 1.0], n) * mant(rng, n) * 2.0 ** rng.integers(lo, hi + 1, n)).astype(F32)
+    bx, by, mx = r(-20, 20), r(-20, 20), r(-30, 30)
+    ax = r(-40, 40)
+    third = n // 3
+    for lane, sl in ((bx, slice(third, 2 * third)), (by, slice(2 * third, n))):
+        p = (lane[sl] * mx[sl]).astype(F32)  # one rounding
+        k = rng.integers(0, 4, len(p)).astype(np.int32)
+        ax[sl] = -(bits32(p).astype(np.int64) + k).astype(U32).view(F32)
+    junk = np.array([QNAN32, 0x7f7fffff, 0xff7fffff, 0x7f800000, 0xff800000], U32).view(F32)
+    my, ay = junk[np.arange(n) % 5], junk[(np.arange(n) + 2) % 5]
+    return bx, by, mx, my, ax, ay
+
+
+def pk_fma_ref(bx, by, mx, my, ax, ay):
+    """(fmaf(b.x, m.x, a.x), fmaf(b.y, m.x, a.x))."""
+    return fma32(bx, mx, ax), fma32(by, mx, ax)
+
+
+def pk_mul_add_ref(bx, by, mx, my, ax, ay):
+    """The control: the product rounded, then the sum."""
+    with np.errstate(all="ignore"):
+        return ((bx * mx).astype(F32) + ax).astype(F32), ((by * mx).astype(F32) + ax).astype(F32)
+
+
+SLAB_SPECIALS = np.array([QNAN32, 0x7f800000, 0xff800000, 0, 0x80000000], U32).view(F32)
+
+
+def slab_inputs(seed=503):
+    """(x, y, z, w, at): f32 planes of slab_near / slab_far, random values of mixed sign and scale, with
+    every way of putting NaN, +inf, -inf, +0, -0 or a random value at each of the four operands (6^4
+    patterns: one, two and three NaN operands among them, and all four) at the elements `at`: one
+    pattern per wave, at lane 0, 31, 32, 63 in turn."""
+    rng = np.random.default_rng(seed)
+    pat = np.array([[(q // 6 ** j) % 6 for j in range(4)] for q in range(6 ** 4)])
+    n = 64 * len(pat)
+    r = lambda k: (rng.choice([-1.0, 1.0], k) * mant(rng, k) * 2.0 ** rng.integers(-30, 31, k)).astype(F32)
+    cols = [r(n) for _ in range(4)]
+    at = np.arange(len(pat)) * 64 + np.array(LANES)[np.arange(len(pat)) % len(LANES)]
+    for j in range(4):
+        special = pat[:, j] < 5
+        cols[j][at[special]] = SLAB_SPECIALS[pat[special, j]]
+    return tuple(cols) + (at,)
+
+
+def slab_ref(x, y, z, w, far):
+    """fmaxf(fmaxf(x, y), fmaxf(z, w)), or the fminf chain: a NaN operand is dropped."""
+    f = np.fmin if far else np.fmax
+    return f(f(x, y), f(z, w))
+
+
+def same_f32(got, want):
+    """Indices where two f32 arrays differ in bits; a NaN matches any NaN, and +0 matches -0 (fmaxf and
+    fminf leave the sign of a zero result open, and the walk only compares the results)."""
+    got, want = np.asarray(got, F32), np.asarray(want, F32)
+    ok = (bits32(got) == bits32(want)) | (np.isnan(got) & np.isnan(want)) | ((got == 0) & (want == 0))
+    return np.flatnonzero(~ok)

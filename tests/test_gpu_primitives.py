@@ -1,10 +1,11 @@
 """The kernel's hand-written f64 primitives (csrc/rt_device.h, csrc/rt_leaf_filter.h) value by value,
 through the probe library (tests/hip/rt_probe.hip): sqrt_g, unit, the scatter finish, RayDiv, reflect,
-refract, range_pm1, sample_key, the Xoshiro256++ draw and Random.float in both instruction forms, and the
-leaf filter.  Every result is compared bit for bit with a correctly rounded numpy reference or with the
+refract, range_pm1, sample_key, the Xoshiro256++ draw and Random.float in both instruction forms, the
+leaf filter, and the BVH walk's f32 slab primitives (csrc/rt_slab.h).  Every result is compared bit for bit with a correctly rounded numpy reference or with the
 oracle's stream (tests/probe_support.py); the inputs sit on the guards, on rounding midpoints and in
 single lanes of otherwise ordinary waves, where a whole render never puts them.  The f32 fast mode's bits
-are unspecified and not probed."""
+are unspecified and not probed; the slab primitives are f32 in both modes, and their bits are what the
+padding certificate of csrc/rt_bvh.cpp assumes."""
 import numpy as np
 import pytest
 
@@ -158,3 +159,66 @@ def test_leaf_filter_device_equals_host(tmp_path):
     bad = np.flatnonzero(got != host)
     assert len(bad) == 0, f"{len(bad)} of {len(host)} differ, first: case {bad[0]} " \
                           f"{[float(c[bad[0]]).hex() for c in cases]} device {got[bad[0]]} host {host[bad[0]]}"
+
+
+# ---- the walk's f32 slab primitives ----------------------------------------------------------------------------
+def test_rcp_clamp():
+    """v_rcp_f32 + v_med3: within 1 ulp of the correctly rounded 1 / x wherever 1 / x is normal and inside
+    the clamp (the padding certificate's assumption); +-1e30 with the operand's sign for +-0, denormals and
+    every operand below 2^-100; in the binade between, one or the other; +-0 for +-inf; at most 2^-126 in
+    size, sign kept, where 1 / x is denormal; and for a NaN what rt_slab.h says."""
+    x = ps.rcp_inputs()
+    got = ps.f32_of(ps.run("rcp_clamp", ps.f32_plane(x))[0])
+    normal, tiny, inf, nan = ps.rcp_classes(x)
+    err = ps.rcp_ulp_error(got[normal], x[normal])
+    worst = int(np.argmax(err))
+    print(f"rcp_clamp: largest error {err.max():.4f} ulp at x = {float(x[normal][worst]).hex()}, "
+          f"{(err > 0.5).mean():.3f} of the results not correctly rounded; NaN -> {sorted(set(map(hex, ps.bits32(got[nan]))))}")
+    assert err.max() <= 1.0
+    big = np.float32(1e30)
+    assert np.array_equal(got[tiny], np.where(np.signbit(x[tiny]), -big, big)), "zeros, denormals, |x| < 2^-100: +-1e30, the operand's sign"
+    edge = (np.abs(x) >= np.float32(2.0 ** -100)) & (np.abs(x) < np.float32(2.0 ** -99))  # the clamp sets in
+    assert edge.sum() >= 24 and (np.abs(got[edge]) <= big).all() and np.array_equal(np.signbit(got[edge]), np.signbit(x[edge]))
+    assert ((np.abs(got[edge]) == big) | (ps.rcp_ulp_error(got[edge], x[edge]) <= 1.0)).all()
+    assert (np.abs(got[edge]) == big).any() and (np.abs(got[edge]) < big).any()
+    assert (got[inf] == 0).all() and np.array_equal(np.signbit(got[inf]), np.signbit(x[inf])), "+-inf: +-0"
+    rest = ~(normal | tiny | inf | nan | edge)  # 1 / x is denormal
+    assert rest.sum() >= 32 and (np.abs(got[rest]) <= np.float32(2.0 ** -126)).all()
+    assert ((got[rest] == 0) | (np.signbit(got[rest]) == np.signbit(x[rest]))).all()
+    assert nan.sum() >= 26 and (got[nan] == -big).all(), "a NaN component, quiet or signalling, of either sign: -1e30 (rt_slab.h)"
+
+
+def test_pk_fma_lo_is_two_single_rounded_fmas_of_the_low_halves():
+    cols = ps.pk_fma_inputs()
+    got = ps.run("pk_fma_lo", *[ps.f32_plane(c) for c in cols])
+    for lane, want in zip("xy", ps.pk_fma_ref(*cols)):
+        g = ps.f32_of(got["xy".index(lane)])
+        bad = np.flatnonzero(ps.bits32(g) != ps.bits32(want))
+        assert len(bad) == 0, f"pk_fma_lo.{lane}: {len(bad)} of {len(want)} differ, first at {bad[0]}: " \
+                              f"b {[float(cols[j][bad[0]]).hex() for j in (0, 1)]} m.x {float(cols[2][bad[0]]).hex()} " \
+                              f"a.x {float(cols[4][bad[0]]).hex()} device {float(g[bad[0]]).hex()} reference {float(want[bad[0]]).hex()}"
+        assert np.isfinite(g).all(), "the high halves of m and a (NaN, inf, FLT_MAX) are never read"
+
+
+def test_control_mul_then_add_is_seen_to_differ():
+    """b * m + a in two roundings on the device equals numpy's same expression, and differs from the fma
+    in at least 20% of the elements of each lane: the comparison resolves the fma's single rounding."""
+    cols = ps.pk_fma_inputs()
+    got = ps.run("pk_mul_add", *[ps.f32_plane(c) for c in cols])
+    for j, (two, one) in enumerate(zip(ps.pk_mul_add_ref(*cols), ps.pk_fma_ref(*cols))):
+        g = ps.f32_of(got[j])
+        assert np.array_equal(ps.bits32(g), ps.bits32(two)), f"lane {j}: {int((ps.bits32(g) != ps.bits32(two)).sum())} differ"
+        differ = np.mean(ps.bits32(g) != ps.bits32(one))
+        print(f"control differs from the fma in {differ:.3f} of lane {j}")
+        assert differ >= 0.20
+
+
+@pytest.mark.parametrize("far", [False, True])
+def test_slab_near_and_far_are_the_fmaxf_and_fminf_chains(far):
+    x, y, z, w, _ = ps.slab_inputs()
+    op = "slab_far" if far else "slab_near"
+    got = ps.f32_of(ps.run(op, *[ps.f32_plane(c) for c in (x, y, z, w)])[0])
+    want = ps.slab_ref(x, y, z, w, far)
+    bad = ps.same_f32(got, want)
+    assert len(bad) == 0, f"{op}: {len(bad)} of {len(want)} differ, first at {bad[0]}: " \
+                          f"{[float(c[bad[0]]) for c in (x, y, z, w)]} device {got[bad[0]]} reference {want[bad[0]]}"

@@ -1,7 +1,8 @@
 """CPU checks of what the device-primitive tests stand on (tests/probe_support.py): the input generators
 produce the operand classes they promise, the numpy restatements equal the oracle, the injected RNG
 states give the words they are built for, the control expression differs from the division, the
-oracle's state functions continue its seeded ones, and the probe library builds and loads."""
+oracle's state functions continue its seeded ones, the operands of the walk's f32 slab primitives cover
+their classes, and the probe library builds and loads."""
 import ctypes as C
 
 import numpy as np
@@ -35,6 +36,9 @@ def test_probe_library_builds_and_loads():
     assert ps.planes("raydiv") == (2, 1, False, False)
     assert ps.planes("leaf_behind") == (4, 1, False, True)
     assert ps.planes("state_uniform_lean") == (5, 1, True, False)
+    assert ps.planes("rcp_clamp") == (1, 1, False, False) and ps.planes("slab_far") == (4, 1, False, False)
+    assert ps.planes("pk_fma_lo") == ps.planes("pk_mul_add") == (6, 2, False, False)
+    assert L.rt_probe_run(ps.OPS["pk_fma_lo"], 1, 6 * 256 * 8, 1, 2 * 256 * 8 - 1, 256, 0, None) == -4
     # refused before anything is launched: unknown op, ragged n, too many draws, short buffers
     assert L.rt_probe_run(99, 1, 8, 1, 8, 256, 0, None) == -1
     assert L.rt_probe_run(ps.OPS["sqrt"], 1, 1 << 20, 1, 1 << 20, 100, 0, None) == -2
@@ -299,3 +303,74 @@ def test_masks_and_masked_reference():
     assert out[:, 0].tolist() == list(range(100, 108))
     assert out[:, 1].tolist() == [7, 7, 108, 7, 7, 109, 7, 7]
     assert out[:, 2].tolist() == [7] * 8
+
+
+# ---- the walk's f32 slab primitives ----------------------------------------------------------------------------
+def test_rcp_inputs_cover_every_exponent_and_the_edges():
+    x = ps.rcp_inputs()
+    b = ps.bits32(x)
+    e = (b >> np.uint32(23)) & np.uint32(0xff)
+    for sign in (0, 1):
+        assert len(np.unique(e[(b >> np.uint32(31)) == sign])) == 256, "every exponent, both signs"
+    for edge in (0, 1, 0x007fffff, 0x00800000, 0x7f7fffff, 0x7f800000, ps.QNAN32):
+        assert (b == edge).any() and (b == (edge | 0x80000000)).any(), hex(edge)
+    for k in (1, 127, 254):  # powers of two with both neighbours
+        assert all((b == (k << 23) + d).any() for d in (-1, 0, 1))
+    normal, tiny, inf, nan = ps.rcp_classes(x)
+    assert normal.sum() >= 5000 and tiny.sum() >= 600 and inf.sum() == 2 and nan.sum() >= 26
+    ax = np.abs(x[~nan].astype(np.float64))
+    assert ((ax < ps.FLT_MIN) & (ax > 0)).sum() >= 24 and ((ax >= 2.0 ** -100) & (ax < 2.0 ** -99)).sum() >= 24
+    assert (np.isfinite(ax) & (ax > 2.0 ** 126)).sum() >= 32, "operands whose reciprocal is denormal"
+    # the error measure: 0 for the correctly rounded reciprocal, 1 for its neighbour next to a power of two
+    ok = x[normal]
+    want = (1.0 / ok.astype(np.float64)).astype(np.float32)
+    assert ps.rcp_ulp_error(want, ok).max() <= 0.5
+    assert 0.5 <= ps.rcp_ulp_error(np.nextafter(want, np.float32(np.inf)), ok).min() and \
+        ps.rcp_ulp_error(np.nextafter(want, np.float32(np.inf)), ok).max() <= 1.5 + 1e-9
+    # and the model's reciprocal (slab_support.rcp_clamp) obeys what the device test asks of the device
+    model = ps.rcp_clamp(x)
+    assert ps.rcp_ulp_error(model[normal], ok).max() <= 0.5
+    assert np.array_equal(model[tiny], np.where(np.signbit(x[tiny]), np.float32(-1e30), np.float32(1e30)))
+
+
+def test_pk_fma_inputs_cancel_and_the_control_differs():
+    cols = ps.pk_fma_inputs()
+    bx, by, mx, my, ax, ay = cols
+    assert all(c.dtype == np.float32 and len(c) == 1 << 14 for c in cols)
+    assert np.isfinite(np.stack([bx, by, mx, ax])).all()
+    assert not np.isfinite(my).all() and not np.isfinite(ay).all() and np.isnan(my).any() and np.isnan(ay).any()
+    assert (np.abs(my[np.isfinite(my)]) == ps.FLT_MAX).all(), "finite junk is large"
+    one, two = ps.pk_fma_ref(*cols), ps.pk_mul_add_ref(*cols)
+    third = len(bx) // 3
+    with np.errstate(all="ignore"):
+        small = np.abs(one[0][third:2 * third]) <= np.abs(bx * mx)[third:2 * third] * 2.0 ** -20
+    assert small.all(), "the x lane's middle third cancels to a residual"
+    for j in range(2):
+        differ = np.mean(ps.bits32(one[j]) != ps.bits32(two[j]))
+        print(f"lane {j}: two roundings differ from one in {differ:.3f}")
+        assert differ >= 0.20
+    # fma32 itself, against exact rational arithmetic on a sample
+    from fractions import Fraction as F
+    for i in list(range(0, len(bx), 97)) + list(range(third, third + 64)):
+        exact = F(float(bx[i])) * F(float(mx[i])) + F(float(ax[i]))
+        want = np.float32(exact.numerator / exact.denominator) if exact else np.float32(0)
+        assert one[0][i] == want, (i, one[0][i], want)
+
+
+def test_slab_inputs_hold_every_pattern_of_specials():
+    x, y, z, w, at = ps.slab_inputs()
+    assert len(at) == 6 ** 4 and sorted(set(at % 64)) == list(ps.LANES)
+    cols = np.stack([x, y, z, w])[:, at]
+    nans = np.isnan(cols).sum(axis=0)
+    assert [int((nans == k).sum()) for k in range(5)] == [625, 500, 150, 20, 1]
+    for k in (1, 2, 3):
+        assert (np.isnan(cols[:3]).sum(axis=0) == k).any(), "%d of x, y, z NaN" % k
+    assert (cols == np.inf).any(axis=1).all() and (cols == -np.inf).any(axis=1).all()
+    zero = cols == 0
+    assert (zero & np.signbit(cols)).any(axis=1).all() and (zero & ~np.signbit(cols)).any(axis=1).all()
+    # the reference drops NaN operands: NaN only where all four are
+    for far in (False, True):
+        ref = ps.slab_ref(x, y, z, w, far)
+        assert np.isnan(ref).sum() == 1 and np.isnan(ref[at][nans == 4]).all()
+    assert len(ps.same_f32(np.float32([0.0, np.nan, 1.0]), np.float32([-0.0, np.nan, 1.0]))) == 0
+    assert ps.same_f32(np.float32([1.0, np.inf]), np.float32([np.nextafter(np.float32(1), np.float32(2)), -np.inf])).tolist() == [0, 1]
