@@ -553,6 +553,65 @@ int rt_occluded_rays(rt_context* ctx, const void* d_origins, const void* d_ends,
                      uint32_t ray_stride, uint64_t n_rays, double t_min, double t_max,
                      const void* d_intervals, uint32_t flags,
                      uint8_t* d_occluded, uint64_t* d_mask, void* d_stats, void* stream);
+/* ---- radiance queries: rayColor of caller-supplied rays, bit-exact ----------------
+ * Camera.rayColor (camera.zig:148-183) — the bounce loop over HittableList.hit, Material.scatter and the
+ * sky — for n_rays rays in DEVICE memory, in the reference's f64 arithmetic and draw order, bit for bit.
+ * d_origins, d_directions, ray_stride: exactly as rt_trace_rays (f64, stride in doubles, 0 means 3, 1
+ * and 2 invalid; directions used as given, not normalised).
+ *
+ * Per ray q and sample s in [sample_begin, sample_begin + sample_count): a fresh Xoshiro256++ stream is
+ * seeded from rt_sample_key(seed, ray_base + q, s) — the renderer's key with the ray's id in the pixel's
+ * place — and the colour is rayColor(ray_q) with bounceMax = bounce_max and Scene.interval = (t_min,
+ * t_max) for every segment.  No draw is made before the first world.hit: the caller made the ray.
+ * bounce_max == 0 gives black.  bounce_max is any uint32_t; the cost is proportional to it.
+ *
+ * d_sum ([n][3] f64, the colour accumulator's layout, may be NULL): the colours are added in sample
+ * order to the unscaled sums, sum = sum + colour, one addition per component and sample.  sample_begin
+ * == 0 starts a ray: its entry is overwritten and not read.  sample_begin > 0 continues from the stored
+ * sums.  rt_accum_resolve scales the buffer or packs it to RGB8.  So
+ *   - any split of [0, n) into consecutive calls leaves the bits of the one call;
+ *   - any split of a batch into consecutive sub-batches with matching ray_base leaves the bits of the
+ *     one batch;
+ *   - no result depends on the grid, the tree, the kernel form or which lane ran a ray.
+ *
+ * d_states (DEVICE, [n][4] uint64, may be NULL): ray q's one sample uses these four words as its
+ * Xoshiro256++ state in place of seeding from the key — how a caller who drew from a stream before the
+ * ray existed hands the stream on, as the reference's getRay does to rayColor.  sample_count must be 1;
+ * seed and ray_base are unused; sample_begin still decides overwrite or add.  Fed getRay's rays and the
+ * states after getRay's draws, the call returns the renderer's own 1-spp image, bit for bit.  (An
+ * all-zero state never leaves randomUnitVec's rejection loop, in the reference as here.)
+ *
+ * NaN and infinite components, zero directions and empty, negative or NaN intervals are legal: the
+ * result is what the reference's operations give (a zero direction misses everything and its sky
+ * colour is NaN), and the call neither faults nor hangs.
+ *
+ * d_stats (DEVICE, 3 x uint64, may be NULL) is atomically incremented: [0] paths (n_rays x
+ * sample_count), [1] segments (the world.hit calls: exact and deterministic), [2] segments the list scan
+ * resolved (every segment when the context walks the list).
+ *
+ * Always parity arithmetic, whatever rt_context_set_precision says; instrumented contexts are accepted;
+ * the structure the context holds is walked as it is, never rebuilt or trained.  The tree's domain rule
+ * is rt_trace_rays' (csrc/rt_trace.h), applied to every segment as used.
+ *
+ * Launch: asynchronous on `stream`, one kernel, a plain one-stream call (a pending deferred reduce pass
+ * runs first), no workspace; rt_context_kernel_times reports it as sample_ms, with reduce_ms 0.
+ * n_rays == 0 or sample_count == 0: RT_OK, nothing is touched.  d_sum and d_stats both NULL: RT_OK, no
+ * launch.
+ * RT_ERR_INVALID, each answered before any device is touched: null d_origins, d_directions or params;
+ * ray_stride 1 or 2; reserved != 0; ray_base + n_rays > 2^32; sample_begin + sample_count > 2^32 - 1;
+ * d_states with sample_count != 1; null ctx; no scene uploaded. */
+typedef struct rt_radiance_params {
+    uint64_t seed;          /* Scene.seed of the streams */
+    uint64_t ray_base;      /* stream id of ray 0: ray q uses id ray_base + q */
+    uint32_t sample_begin;  /* first sample of this call */
+    uint32_t sample_count;  /* samples per ray in this call */
+    uint32_t bounce_max;    /* Camera.bounceMax */
+    uint32_t reserved;      /* must be 0 */
+    double   t_min, t_max;  /* Scene.interval, used for every segment */
+} rt_radiance_params;       /* 48 bytes */
+int rt_radiance_rays(rt_context* ctx, const void* d_origins, const void* d_directions,
+                     uint32_t ray_stride, uint64_t n_rays, const rt_radiance_params* params,
+                     const void* d_states, void* d_sum, void* d_stats, void* stream);
 /* The origin bound of the tree the context holds: rays starting within it (max|o_k| <= bound) may use
  * the tree; rays starting beyond it are exact but cost a scan of the whole list.  0 when the list walk
  * runs. */

@@ -204,6 +204,30 @@ struct OcclusionArgs {
     uint32_t targets;          // RT_OCCLUSION_TARGETS
     uint32_t n_tiles;          // set by rtk_launch_occlusion: tiles of 64 rays, a wave each
 };
+// Radiance queries (rt_radiance_rays): rayColor of n_rays caller-supplied rays, s_count
+// samples each, added in sample order to the unscaled sums sum[q][0..2].  Rays as TraceArgs; one
+// interval for every segment.  Sample s of ray q draws from the stream keyed
+// sample_key(seed_mix, ray_base + q, s_begin + s), or — `states` != nullptr, s_count == 1 — continues
+// the Xoshiro256++ state states[q][0..3].  s_begin == 0 overwrites sum[q], s_begin > 0 continues from
+// it.  The radiance kernels (radiance_kernel*, rt_kernel.hip) take this as their LAST argument, as the
+// trace kernels do.
+struct RadianceArgs {
+    const double* origins;
+    const double* directions;
+    const unsigned long long* states;  // [n][4] or nullptr
+    double* sum;               // [n][3] unscaled sums, or nullptr (stats only)
+    unsigned long long* stats; // {paths, segments, segments resolved by the list scan} or nullptr
+    unsigned long long* ctr;   // kCtrBytes: [kErrWord] error word (RTZIG_BOUNDS debug builds)
+    double t_min, t_max;
+    uint64_t seed_mix;         // sm_mix(seed), as KernelParams::seed_mix
+    uint64_t ray_base;         // stream id of ray 0; ray_base + n_rays <= 2^32
+    uint64_t n_rays;           // > 0, <= 2^32
+    uint32_t ray_stride;       // doubles between rays, >= 3
+    uint32_t n_tiles;          // set by rtk_launch_radiance: tiles of 64 rays, queued per wave
+    uint32_t s_begin, s_count; // s_count > 0; s_begin + s_count <= 2^32 - 1
+    uint32_t bounce_max;
+    uint32_t pad;
+};
 // rt_accum_select: an ordered stream compaction in three launches, none of which
 // waits on another block.  Blocks of kSelBlock threads, one pixel each.  Scratch (the context's):
 // [blocks] u32 block counts (the scan turns them into exclusive offsets in place), then, 8-B aligned,
@@ -241,6 +265,12 @@ constexpr uint32_t kPad = 4;               // sphere list padded to a multiple o
 #define RTZIG_RUV_TRIPS 3
 #endif
 constexpr int kRuvTrips = RTZIG_RUV_TRIPS;  // randomUnitVec rejection trips per loop iteration (path_loop; 2, 4 slower)
+// ... and of radiance_loop (rt_radiance_rays): the same capped scheme by default; 0 is
+// the A/B form, a per-lane loop that draws until every pending lane of the wave has accepted
+#ifndef RTZIG_RADIANCE_TRIPS
+#define RTZIG_RADIANCE_TRIPS RTZIG_RUV_TRIPS
+#endif
+constexpr int kRadianceTrips = RTZIG_RADIANCE_TRIPS;
 constexpr const char* kDefaultVariant = "smem_u4";  // see variant_choice() in rt_kernel.hip
 
 // Geometry walked by every lane for every ray: 32 B, one LDS broadcast pair per sphere.
@@ -451,6 +481,14 @@ extern "C" hipError_t rtk_launch_trace(const rtk::KernelParams* p, const rtk::Bv
 // chosen and sized exactly as rtk_launch_trace chooses the trace kernel.  One launch, no workspace.
 extern "C" hipError_t rtk_launch_occlusion(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
                                            const rtk::OcclusionArgs* oa, hipStream_t stream, const char** name);
+// Radiance queries (rtk::RadianceArgs): the radiance kernel of the structure the context holds, chosen
+// and staged exactly as rtk_launch_trace chooses the trace kernel; the grid is the trace launcher's for
+// ra->n_tiles tiles, which the waves queue and refill from (RTZIG_RADIANCE_BLOCKS, a test hook read per
+// call, caps its blocks and changes no result).  One launch, no workspace.  Only p->n_spheres and
+// p->n_pad are read.
+extern "C" hipError_t rtk_launch_radiance(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                          const rtk::MatRec* mat, const rtk::RadianceArgs* ra, hipStream_t stream,
+                                          const char** name);
 // rt_accum_select's three launches (count, scan, scatter) over a->n pixels.
 extern "C" hipError_t rtk_launch_select(const rtk::SelectArgs* a, hipStream_t stream);
 // out[q] = accum[q] * (1.0 / counts[q]) (0 where counts[q] == 0), formats as rtk_launch_resolve.

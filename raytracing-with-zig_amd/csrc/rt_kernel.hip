@@ -54,6 +54,12 @@
 //   any-hit mode (BvhWalker::any_hit, world_any): the interval never shrinks and a lane leaves at its
 //   first accepted root.  Routing as the trace kernels.  New entry points only; the existing kernels
 //   compile to the same instructions as before.
+//
+// Radiance queries (rt_radiance_rays, rt_kernel.h RadianceArgs): radiance_kernel (list walk) and
+//   radiance_kernel_bvh run radiance_loop — rayColor of caller-supplied rays, one lane per path, its
+//   samples added in order in registers, free lanes refilled from the wave's own queue of tiles.  Every
+//   segment is routed as a trace ray; the shading is path_loop's, restated.  New entry points only; the
+//   existing kernels compile to the same instructions as before.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -2663,6 +2669,286 @@ __global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) 
                          }, geo_g, oa, (double)b.origin_bound);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Radiance queries (rt_radiance_rays, rt_kernel.h RadianceArgs): Camera.rayColor
+// (camera.zig:148-183) of rays the caller supplies — the bounce loop over HittableList.hit,
+// Material.scatter and the sky — s_count samples per ray, added in sample order to the ray's sums.
+// One lane holds one path and advances it by one segment per iteration, walk then shade: path_loop's
+// body without units, rings, seed windows or suspension.  A lane owns its ray for all of the call's
+// samples and keeps the three sums in registers: when a sample ends (sky, absorbed, bounce limit) it
+// adds the colour and starts the next sample of the same ray, and after the last one it stores the
+// sums and is free.
+// Refill: a wave owns the tiles wave0 + k x waves of 64 consecutive rays (trace_loop's striding) as
+// ONE queue of rays; in every iteration its free lanes take the queue's next rays, lane by rank among
+// the free lanes (the prefix count of their ballot) from a wave-uniform cursor.  No atomics, no LDS
+// hand-off, nothing waits on another wave; the loop ends when the queue is empty and no lane holds a
+// path.  Which lane runs a ray changes no bit: a path reads its own ray, stream and sums only.
+// Every segment is routed as trace_loop routes a ray: trace_tree_ok (rt_trace.h) on the segment as
+// used, the dummy ray for a lane that fails, then world_hit<1> on the real ray behind a wave-uniform
+// ballot.  The list-walk kernels scan every segment.
+// Shading is path_loop's parity arithmetic, restated: the hit record, one shared unit() for the sky,
+// the dielectric and the metal, the scatter finished from the draws of the capped rejection trips
+// (kRadianceTrips per iteration; a lane still rejected stays pending, skips the walk and draws on).
+// ------------------------------------------------------------------------------------------------
+template <bool kTree, class Walker>
+__device__ __forceinline__ void radiance_loop(const KernelParams& p, const Walker& walk,
+                                              const GeoRec* __restrict__ geo_orig, const MatRec* __restrict__ mat_g,
+                                              const RadianceArgs& ra, double origin_bound) {
+    const uint32_t lane = lane_id();
+    const uint32_t waves = gridDim.x * (blockDim.x / 64);
+    const uint32_t wave0 = __builtin_amdgcn_readfirstlane((threadIdx.x / 64) * gridDim.x + blockIdx.x);
+    const size_t stride = ra.ray_stride;
+    Prof<0> pr;
+    // the wave's queue: the rays of its tiles in tile order; the batch's last tile (partial) is the
+    // last of its owner's queue
+    uint64_t q_len = 0, cursor = 0;  // wave-uniform
+    if (wave0 < ra.n_tiles) {
+        const uint32_t after = ra.n_tiles - 1 - wave0;  // tiles from the wave's first to the batch's last
+        q_len = ((uint64_t)(after / waves) + 1) * 64;
+        if (after % waves == 0) q_len -= (uint64_t)ra.n_tiles * 64 - ra.n_rays;
+    }
+    // per-lane path state
+    bool active = false;  // the lane holds a ray
+    bool start = false;   // ... and begins a sample of it in this iteration
+    size_t q = 0;         // the ray
+    uint32_t s = 0;       // samples of it done in this call
+    v3 sum = mk(0, 0, 0);
+    Rng g;
+    g.s0 = g.s1 = g.s2 = g.s3 = 0;
+    Ray r;
+    r.orig = r.dir = mk(0, 0, 0);
+    v3 att = mk(1, 1, 1);
+    uint32_t bounce = 0;
+    // pending Lambertian / Metal scatter (waiting for its randomUnitVec)
+    bool pending = false, sc_metal = false;
+    double sc_fuzz = 0;
+    v3 sc_nrm = mk(0, 0, 0), sc_refl = mk(0, 0, 0);
+    uint64_t n_paths = 0, n_seg = 0, n_scan = 0;  // this wave's counts (wave-uniform)
+
+    while (true) {
+        // ---- free lanes take the queue's next rays ------------------------------------------------
+        const uint64_t free_m = __ballot(!active);
+        if (free_m != 0 && cursor < q_len) {
+            const uint64_t e = cursor + rank_in(free_m);
+            const size_t qe = ((size_t)wave0 + (size_t)(e >> 6) * waves) * 64 + (size_t)(e & 63);
+            if (!active && e < q_len && bounds_ok(qe < ra.n_rays, ra.ctr) && qe < ra.n_rays) {
+                q = qe;
+                s = 0;
+                active = true;
+                start = true;
+                sum = mk(0, 0, 0);
+                // a call that continues (s_begin > 0) starts from the stored sums
+                if (ra.s_begin != 0 && ra.sum) sum = mk(ra.sum[3 * q], ra.sum[3 * q + 1], ra.sum[3 * q + 2]);
+            }
+            const uint64_t n_free = (uint64_t)__popcll(free_m), left = q_len - cursor;
+            cursor += n_free < left ? n_free : left;
+        }
+        if (__ballot(active) == 0) break;  // the queue is empty (a free lane would have taken) and no lane holds a path
+        // ---- a sample starts: the caller's ray, a fresh stream (or the caller's state) --------------
+        if (start) {
+            r.orig = mk(ra.origins[q * stride], ra.origins[q * stride + 1], ra.origins[q * stride + 2]);
+            r.dir = mk(ra.directions[q * stride], ra.directions[q * stride + 1], ra.directions[q * stride + 2]);
+            if (ra.states) {
+                g.s0 = ra.states[4 * q];
+                g.s1 = ra.states[4 * q + 1];
+                g.s2 = ra.states[4 * q + 2];
+                g.s3 = ra.states[4 * q + 3];
+            } else {
+                g.seed(sample_key(ra.seed_mix, ra.ray_base + q, ra.s_begin + s));
+            }
+            att = mk(1, 1, 1);
+            bounce = 0;
+            start = false;
+        }
+        // ---- randomUnitVec's rejection trips (vec.zig:71-80), at most kRadianceTrips per iteration -
+        bool done = false;
+        v3 col = mk(0, 0, 0);
+        double ux = 0, uy = 0, uz = 0, uls = 1;
+        bool got = false;
+        // one trip for the lanes still drawing; leaves the loop when no lane of the wave is
+#define RTK_RADIANCE_TRIP                            \
+    const bool wr = pending && !got;                 \
+    if (__ballot(wr) == 0) break;                    \
+    if (wr) {                                        \
+        ux = g.range_pm1();                          \
+        uy = g.range_pm1();                          \
+        uz = g.range_pm1();                          \
+        uls = (ux * ux + uy * uy) + uz * uz;         \
+        got = 1e-160 < uls && uls <= 1;              \
+    }
+        if constexpr (kRadianceTrips > 0) {
+#pragma unroll
+            for (int k = 0; k < kRadianceTrips; ++k) {
+                RTK_RADIANCE_TRIP
+            }
+        } else {  // the per-lane loop: every pending lane draws until it accepts
+            while (true) {
+                RTK_RADIANCE_TRIP
+            }
+        }
+#undef RTK_RADIANCE_TRIP
+        if (got) {  // finish the scatter
+            const double l = sqrt_normal(uls);  // |p|^2 in (1e-160, 1] (vec.zig:76)
+            const SharedRcp rl(l);
+            const v3 ruv = mk(rl.div(ux), rl.div(uy), rl.div(uz));  // p / sqrt(|p|^2), true divisions
+            bool absorbed = false;
+            if (!sc_metal) {
+                r.dir = sc_nrm + ruv;
+                if (near_zero(r.dir)) r.dir = sc_nrm;
+            } else {
+                r.dir = sc_refl + muls(ruv, sc_fuzz);  // unit(reflect(ray.dir, n)) + fuzz * ruv
+                absorbed = !(dot(r.dir, sc_nrm) > 0);  // absorbed -> black
+            }
+            pending = false;
+            if (absorbed) {
+                done = true;
+            } else {
+                ++bounce;
+            }
+        }
+        // ---- one ray segment per ready lane (rayColor's loop body, camera.zig:153-177) -------------
+        bool seg = false, scanned = !kTree;  // this lane traced a segment / the list scan resolved it
+        if (active && !done && !pending) {
+            if (bounce >= ra.bounce_max) {
+                done = true;  // too many bounces -> black (camera.zig:181)
+            } else {
+                seg = true;
+                double t;
+                int k;
+                __builtin_amdgcn_s_setprio(2);
+                if constexpr (kTree) {
+                    const double o3[3] = {r.orig.x, r.orig.y, r.orig.z}, d3[3] = {r.dir.x, r.dir.y, r.dir.z};
+                    const bool ok = trace_tree_ok(o3, d3, ra.t_min, ra.t_max, origin_bound);
+                    scanned = !ok;
+                    const double nan = __builtin_nan("");
+                    Ray rw;
+                    rw.orig = mk(ok ? r.orig.x : nan, ok ? r.orig.y : nan, ok ? r.orig.z : nan);
+                    rw.dir = mk(ok ? r.dir.x : 1.0, ok ? r.dir.y : 0.0, ok ? r.dir.z : 0.0);
+                    k = walk(rw, ok ? ra.t_min : 1.0, ok ? ra.t_max : -1.0, &t, pr);
+                    if (__ballot(scanned) != 0) {
+                        if (scanned) k = world_hit<1>(geo_orig, p.n_pad, r, ra.t_min, ra.t_max, &t);
+                    }
+                } else {
+                    k = walk(r, ra.t_min, ra.t_max, &t, pr);
+                }
+                __builtin_amdgcn_s_setprio(1);
+                // path_loop's shading block: every shaded lane computes the hit record and material,
+                // the sky lanes on sphere 0's records (unused), and one unit() serves the sky, the
+                // dielectric and the metal
+                if (k >= 0 && !bounds_ok((uint32_t)k < p.n_spheres, ra.ctr)) k = -1;
+                const bool hit = k >= 0;
+                const uint32_t kk = hit ? (uint32_t)k : 0u;
+                const GeoRec sg = geo_orig[kk];
+                const MatRec m = mat_g[kk];
+                // hit record (sphere.zig:44-53)
+                const v3 pt = r.orig + muls(r.dir, t);
+                const v3 outward = muls(pt - mk(sg.cx, sg.cy, sg.cz), m.inv_r);
+                const bool front = dot(r.dir, outward) < 0;
+                const v3 nrm = front ? outward : -outward;
+                const uint32_t kind = m.kind;
+                const double ri = front ? m.inv_ior : m.ior;       // dielectric: 1.0 / ior precomputed (same bits)
+                const double r0 = front ? m.r0_front : m.r0_back;  // Schlick ((1-ri)/(1+ri))^2, host
+                if (hit && kind == 1) r.dir = reflect(r.dir, nrm);
+                const v3 u = unit(r.dir);
+                sc_nrm = nrm;
+                sc_refl = u;
+                sc_fuzz = m.fuzz;
+                sc_metal = kind == 1;
+                r.orig = pt;
+                if (!hit) {
+                    // sky gradient (camera.zig:171-177)
+                    const double a = 0.5 * (u.y + 1.0);
+                    const v3 sky = muls(mk(1, 1, 1), 1.0 - a) + muls(mk(0.5, 0.7, 1), a);
+                    col = att * sky;
+                    done = true;
+                } else if (kind <= 1) {
+                    // Lambertian (material.zig:27-39) / Metal (:55-68): attenuation = albedo; an absorbed
+                    // metal ray returns black whatever `att` is
+                    att = att * mk(m.albedo[0], m.albedo[1], m.albedo[2]);
+                    pending = true;
+                } else {  // Dielectric.scatter (material.zig:82-110), attenuation (1,1,1)
+                    const double cos_t = __builtin_fmin(dot(-u, nrm), 1.0);
+                    const double sin_t = sqrt_g(1.0 - cos_t * cos_t);
+                    const bool cannot = ri * sin_t > 1.0;
+                    const double approx = r0 + (1 - r0) * zig_pow5(1 - cos_t);
+                    // short-circuit `or` (material.zig:94): draw only if refraction is possible
+                    r.dir = (cannot || approx > g.uniform()) ? reflect(u, nrm) : refract(u, nrm, ri);
+                    ++bounce;
+                }
+            }
+        }
+        __builtin_amdgcn_s_setprio(0);
+        n_seg += (uint64_t)__popcll(__ballot(seg));
+        n_scan += (uint64_t)__popcll(__ballot(seg && scanned));
+        n_paths += (uint64_t)__popcll(__ballot(done));
+        // ---- a sample ends: pixelColor += rayColor(ray) (camera.zig:135), then the next sample or the store
+        if (done) {
+            sum = sum + col;
+            ++s;
+            if (s == ra.s_count) {
+                if (ra.sum) {
+                    ra.sum[3 * q] = sum.x;
+                    ra.sum[3 * q + 1] = sum.y;
+                    ra.sum[3 * q + 2] = sum.z;
+                }
+                active = false;
+            } else {
+                start = true;
+            }
+        }
+    }
+    // {paths, segments, segments resolved by the list scan}: one vector atomic per wave and word
+    if (ra.stats && lane == 0 && n_paths) {
+        atomicAdd(ra.stats, (unsigned long long)n_paths);
+        if (n_seg) atomicAdd(ra.stats + 1, (unsigned long long)n_seg);
+        if (n_scan) atomicAdd(ra.stats + 2, (unsigned long long)n_scan);
+    }
+}
+
+// The list walk, staged as trace_kernel.
+template <bool kLds>
+__global__ __launch_bounds__(kBlock) void radiance_kernel(KernelParams p, const GeoRec* __restrict__ geo_g,
+                                                          const MatRec* __restrict__ mat_g, RadianceArgs ra) {
+    extern __shared__ GeoRec lds_geo[];
+    const GeoRec* geo = geo_g;
+    if constexpr (kLds) {
+        for (uint32_t k = threadIdx.x; k < p.n_pad; k += blockDim.x) lds_geo[k] = geo_g[k];
+        __syncthreads();
+        geo = lds_geo;
+    }
+    radiance_loop<false>(p, LinearWalker<4>{geo, p.n_pad, p.n_spheres}, geo_g, mat_g, ra, 0.0);
+}
+
+// The BVH walk, the tree staged as trace_kernel_bvh stages it.  KernelParams and BvhArgs are the first
+// two arguments: the walker reads the always-list from the kernarg segment at their offsets.
+template <bool kLdsScene>
+__global__ __launch_bounds__(kBlockBvh) __attribute__((amdgpu_waves_per_eu(4))) void radiance_kernel_bvh(
+    KernelParams p, BvhArgs b, const GeoRec* __restrict__ geo_g, const MatRec* __restrict__ mat_g, RadianceArgs ra) {
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const size_t scene_bytes = kLdsScene ? (size_t)bvh_leaves_offset(b.n_nodes) + (size_t)b.n_leaves * sizeof(BvhLeaf) : 0;
+    using Stack = std::conditional_t<kLdsScene, StackEntry, int32_t>;
+    using Walker = BvhWalker<kLdsScene, kBlockBvh, Stack, false>;
+    Stack* stack = (Stack*)(lds_raw + scene_bytes);
+    stack[threadIdx.x] = (Stack)Walker::kEnd;  // entry 0 of this lane's stack: popping it ends the walk
+    const BvhNode* nodes = b.nodes;
+    const BvhLeaf* leaves = b.leaves;
+    if constexpr (kLdsScene) {
+        BvhNode* ln = (BvhNode*)lds_raw;
+        BvhLeaf* ll = (BvhLeaf*)(lds_raw + bvh_leaves_offset(b.n_nodes));
+        for (uint32_t k = threadIdx.x; k < b.n_nodes; k += blockDim.x) ln[k] = b.nodes[k];
+        for (uint32_t k = threadIdx.x; k < b.n_leaves; k += blockDim.x) ll[k] = b.leaves[k];
+        __syncthreads();
+        nodes = ln;
+        leaves = ll;
+    }
+    radiance_loop<true>(p, Walker{nodes, leaves, b.always_geo, b.always_sid, b.n_always, stack + threadIdx.x, b.origin_bound,
+                                  geo_g, p.n_pad
+#if RTZIG_BOUNDS
+                                  , b.n_nodes * (uint32_t)sizeof(BvhNode), (uint32_t)(b.n_leaves * sizeof(BvhLeaf)), b.stack_depth, ra.ctr
+#endif
+                        }, geo_g, mat_g, ra, (double)b.origin_bound);
+}
+
 // Direct mode's second pass (rt_kernel.h "Work units"): thread q adds pixel q's stored colors in
 // sample order — pixelColor += rayColor(ray), camera.zig:133-136, from pixelColor = 0 — then
 // scales (:137) and writes linear f64 or the fused Color.toRgb bytes.  A wave's loads of one sample
@@ -3305,6 +3591,63 @@ extern "C" hipError_t rtk_launch_occlusion(const rtk::KernelParams* p, const rtk
     };
     return lds_scene ? launch(occlusion_kernel_bvh<true>, "bvh_lds(occlusion)")
                      : launch(occlusion_kernel_bvh<false>, "bvh_global(occlusion)");
+}
+
+// Radiance queries: rtk_launch_trace's choice of structure, LDS plan and grid, for the radiance kernels.
+// The grid is a wave per tile up to the resident grid; beyond it the waves' queues hold several tiles.
+// RTZIG_RADIANCE_BLOCKS=<n> (test hook, read per call) caps the blocks: any grid gives the same bits.
+extern "C" hipError_t rtk_launch_radiance(const rtk::KernelParams* p, const rtk::BvhArgs* b, const rtk::GeoRec* geo,
+                                          const rtk::MatRec* mat, const rtk::RadianceArgs* ra, hipStream_t stream,
+                                          const char** name) {
+    using namespace rtk;
+    if (ra->n_rays == 0 || ra->s_count == 0) return hipSuccess;
+    if (ra->ray_stride < 3 || !ra->origins || !ra->directions || ra->n_rays > (1ull << 32) ||
+        (ra->states && ra->s_count != 1))
+        return hipErrorInvalidValue;
+    RadianceArgs a = *ra;
+    a.n_tiles = (uint32_t)((a.n_rays + 63) / 64);
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+        cus = 256;
+    uint64_t cap_blocks = UINT64_MAX;
+    if (const char* e = std::getenv("RTZIG_RADIANCE_BLOCKS")) {
+        const long v = std::atol(e);
+        if (v > 0) cap_blocks = (uint64_t)v;
+    }
+    // blocks: a wave per tile, at least one block per CU while tiles last, at most the resident grid
+    auto grid_of = [&](uint32_t block, uint64_t cap) {
+        const uint64_t need = ((uint64_t)a.n_tiles + block / 64 - 1) / (block / 64);
+        const uint64_t spread = a.n_tiles < (uint32_t)cus ? a.n_tiles : (uint64_t)cus;
+        uint64_t g = need > spread ? need : spread;
+        g = g < cap ? g : cap;
+        return (uint32_t)(g < cap_blocks ? g : cap_blocks);
+    };
+    if (b == nullptr) {
+        const Variant& v = variant_choice(p->n_pad <= kMaxLdsSpheres, p->n_pad);
+        const size_t shmem = list_walk_lds(v.lds, p->n_pad, false);  // no seed window
+        auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+            const uint64_t cap = persistent_blocks(kernel, shmem);
+            if (name) *name = nm;
+            hipLaunchKernelGGL(kernel, dim3(grid_of(kBlock, cap)), dim3(kBlock), shmem, stream, *p, geo, mat, a);
+            return hipGetLastError();
+        };
+        return v.lds ? launch(radiance_kernel<true>, "lds_u4(radiance)") : launch(radiance_kernel<false>, "smem_u4(radiance)");
+    }
+    if (b->stack_depth < 2 || b->stack_depth > (uint32_t)kMaxDepthBvh) return hipErrorInvalidValue;
+    const uint32_t block = (uint32_t)kBlockBvh;
+    const auto [lds_scene, scene_bytes, stack_bytes] = bvh_lds_plan(b->n_nodes, b->n_leaves, b->stack_depth, block, kLdsSceneBudget);
+    const size_t shmem = (lds_scene ? scene_bytes : 0) + stack_bytes;
+    auto launch = [&](auto kernel, const char* nm) -> hipError_t {
+        uint32_t cap32 = 0;
+        const hipError_t ea = rtk_resident_blocks((const void*)kernel, (int)block, shmem, &cap32);
+        if (ea != hipSuccess) return ea;
+        if (name) *name = nm;
+        hipLaunchKernelGGL(kernel, dim3(grid_of(block, cap32)), dim3(block), shmem, stream, *p, *b, geo, mat, a);
+        return hipGetLastError();
+    };
+    return lds_scene ? launch(radiance_kernel_bvh<true>, "bvh_lds(radiance)")
+                     : launch(radiance_kernel_bvh<false>, "bvh_global(radiance)");
 }
 
 extern "C" hipError_t rtk_launch_gather_reduce(const rtk::GatherReduceArgs* a, hipStream_t stream) {

@@ -1133,6 +1133,66 @@ int rt_occluded_rays(rt_context* ctx, const void* d_origins, const void* d_ends,
     return close_call(ctx, s, ev);
 }
 
+// ---- radiance queries (rt.h) -------------------------------------------------------
+// rt_trace_rays' launch with the radiance kernel in place of the trace kernel: the structure the context
+// holds, always parity arithmetic, no workspace, no training.
+int rt_radiance_rays(rt_context* ctx, const void* d_origins, const void* d_directions, uint32_t ray_stride,
+                     uint64_t n_rays, const rt_radiance_params* params, const void* d_states, void* d_sum,
+                     void* d_stats, void* stream) {
+    // the argument checks that need no context come first, the context last: each answers before
+    // anything touches a device
+    if (!d_origins) { rt_set_last_error("null d_origins"); return RT_ERR_INVALID; }
+    if (!d_directions) { rt_set_last_error("null d_directions"); return RT_ERR_INVALID; }
+    if (!params) { rt_set_last_error("null params"); return RT_ERR_INVALID; }
+    if (ray_stride == 1 || ray_stride == 2) { rt_set_last_error("ray_stride must be 0 or at least 3"); return RT_ERR_INVALID; }
+    if (params->reserved != 0) { rt_set_last_error("params: reserved must be 0"); return RT_ERR_INVALID; }
+    if (n_rays > (1ull << 32) || params->ray_base > (1ull << 32) - n_rays) {
+        rt_set_last_error("ray_base + n_rays exceeds 2^32");
+        return RT_ERR_INVALID;
+    }
+    if (const int rc = check_sample_range(params->sample_begin, params->sample_count)) return rc;
+    if (d_states && params->sample_count != 1) { rt_set_last_error("d_states needs sample_count == 1"); return RT_ERR_INVALID; }
+    if (!ctx) { rt_set_last_error("null context"); return RT_ERR_INVALID; }
+    if (n_rays == 0 || params->sample_count == 0) return RT_OK;
+    if (!d_sum && !d_stats) return RT_OK;  // no launch
+    if (ctx->n_spheres == 0) { rt_set_last_error("no scene uploaded"); return RT_ERR_INVALID; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    int rc = flush_fold(ctx);  // a plain one-stream call: a pending deferred reduce pass runs first
+    if (!rc) rc = ensure_counters(ctx, s);
+    if (rc) return rc;
+    const bool bvh = use_bvh(ctx);
+    rtk::KernelParams p;
+    std::memset(&p, 0, sizeof p);
+    p.n_spheres = ctx->n_spheres;
+    p.n_pad = (ctx->n_spheres + rtk::kPad - 1) / rtk::kPad * rtk::kPad;
+    rtk::RadianceArgs ra{};
+    ra.origins = (const double*)d_origins;
+    ra.directions = (const double*)d_directions;
+    ra.states = (const unsigned long long*)d_states;
+    ra.sum = (double*)d_sum;
+    ra.stats = (unsigned long long*)d_stats;
+    ra.ctr = ctx->d_ctr;
+    ra.t_min = params->t_min;
+    ra.t_max = params->t_max;
+    ra.seed_mix = rtk::sm_mix_hd(params->seed);
+    ra.ray_base = params->ray_base;
+    ra.n_rays = n_rays;
+    ra.ray_stride = ray_stride ? ray_stride : 3;
+    ra.s_begin = params->sample_begin;
+    ra.s_count = params->sample_count;
+    ra.bounce_max = params->bounce_max;
+    hipEvent_t* ev = nullptr;
+    rc = open_call(ctx, s, 1, &ev);
+    if (rc) return rc;
+    if (ev) {
+        HIP_CHECK(hipEventRecord(ev[0], s));
+        ctx->no_reduce[ctx->call_first] = 1;  // no reduce pass: reduce_ms is 0, not the gap between two events
+    }
+    HIP_CHECK(rtk_launch_radiance(&p, bvh ? &ctx->bvh : nullptr, ctx->d_geo, ctx->d_mat, &ra, s, &ctx->last_kernel));
+    return close_call(ctx, s, ev);
+}
+
 int rt_context_origin_bound(rt_context* ctx, double* bound) {
     if (!ctx || !bound) { rt_set_last_error("null context / output"); return RT_ERR_INVALID; }
     // the bound the kernels compare with: the builder's, rounded down to f32 (upload_bvh)

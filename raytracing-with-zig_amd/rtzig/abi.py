@@ -144,8 +144,23 @@ class RtRayHits(C.Structure):
     ]
 
 
+class RtRadianceParams(C.Structure):
+    """rt_radiance_params: the streams, samples, bounce limit and interval of rt_radiance_rays (rt.h)."""
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("ray_base", C.c_uint64),
+        ("sample_begin", C.c_uint32),
+        ("sample_count", C.c_uint32),
+        ("bounce_max", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("t_min", C.c_double),
+        ("t_max", C.c_double),
+    ]
+
+
 DENOISE_PARAMS_SIZE = 56
 RAY_HITS_SIZE = 40
+RADIANCE_PARAMS_SIZE = 48
 TEMPORAL_FRAME_SIZE = 64
 TEMPORAL_PARAMS_SIZE = 48
 SPHERE_SIZE = 80

@@ -75,6 +75,13 @@ class Scene:
         return occluded(self.world, origins, ends, t_min=t_min, t_max=t_max, intervals=intervals, targets=targets,
                         device=device)
 
+    def radiance(self, origins, directions, samples=1, bounce_max=50, ray_base=0, t_min=1e-3, t_max=INF, states=None,
+                 device=0):
+        """rayColor of (n, 3) arrays of rays in this world, on the GPU: the (n, 3) unscaled sums of
+        `samples` samples per ray, streams keyed with the scene's seed (rtzig.radiance)."""
+        return radiance(self.world, origins, directions, samples=samples, bounce_max=bounce_max, seed=self.seed,
+                        ray_base=ray_base, t_min=t_min, t_max=t_max, states=states, device=device)
+
     def visible(self, a, b, eps=1e-3, device=0):
         """Line of sight: no sphere has a root in the open segment (eps, 1) from a[q] to b[q]."""
         return ~occluded(self.world, a, b, t_min=eps, t_max=1.0, targets=True, device=device)
@@ -481,6 +488,56 @@ def occluded(spheres, origins, ends, t_min=1e-3, t_max=INF, intervals=None, targ
     return res
 
 
+def radiance(spheres, origins, directions, samples=1, bounce_max=50, seed=0xdeadbeef, ray_base=0, t_min=1e-3, t_max=INF,
+             states=None, device=0):
+    """Camera.rayColor of caller-supplied rays on one GPU (rt_radiance_rays), bit for bit the reference's
+    f64 result: the (n, 3) unscaled sums of `samples` samples per ray, added in sample order (divide by
+    `samples` for the mean).  origins, directions: (n, 3) arrays, directions used as given.  Sample s of
+    ray q draws from the stream rt_sample_key(seed, ray_base + q, s).  states: None, or (n, 4) uint64
+    Xoshiro256++ states the one sample of each ray continues (samples must be 1)."""
+    import torch
+
+    o = np.ascontiguousarray(origins, np.float64)
+    d = np.ascontiguousarray(directions, np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError("origins and directions must both be (n, 3)")
+    n = o.shape[0]
+    samples, bounce_max, ray_base = int(samples), int(bounce_max), int(ray_base)
+    if samples < 0 or samples >= 2 ** 32 or bounce_max < 0 or bounce_max >= 2 ** 32:
+        raise ValueError("samples and bounce_max must be in [0, 2^32)")
+    if ray_base < 0 or ray_base + n > 2 ** 32:
+        raise ValueError("ray_base + n must be at most 2^32")
+    st = None
+    if states is not None:
+        st = np.ascontiguousarray(states, np.uint64)
+        if st.shape != (n, 4):
+            raise ValueError("states must be (n, 4) uint64")
+        if samples != 1:
+            raise ValueError("states need samples == 1")
+    if n == 0 or samples == 0:
+        return np.zeros((n, 3))
+    ns = len(spheres)
+    arr = spheres if isinstance(spheres, C.Array) else (RtSphere * ns)(*spheres)
+    r = DeviceRenderer(device)
+    try:
+        r.set_scene(arr)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_o = torch.from_numpy(o).to(dev)
+            d_d = torch.from_numpy(d).to(dev)
+            d_st = torch.from_numpy(st.view(np.int64)).to(dev) if st is not None else None
+            sums = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            r.radiance_rays(d_o.data_ptr(), d_d.data_ptr(), n, sums.data_ptr(), sample_count=samples,
+                            bounce_max=bounce_max, seed=seed, ray_base=ray_base, t_min=t_min, t_max=t_max,
+                            d_states_ptr=d_st.data_ptr() if d_st is not None else None, stream_ptr=stream)
+            res = sums.cpu().numpy()  # waits for the stream
+            r.sync()  # reports a failure the kernel recorded
+    finally:
+        r.close()
+    return res
+
+
 def denoise_params(**overrides):
     """rt_denoise_params: the library's defaults (rt_denoise_default_params: levels 2, sigma_l 4,
     sigma_n 32, sigma_a 32, sigma_z 0.05, sigma_h 4, epsilon 1e-6) with the given fields replaced."""
@@ -782,6 +839,24 @@ class DeviceRenderer:
                                         ray_stride, n_rays, t_min, t_max, C.c_void_p(d_intervals_ptr or 0),
                                         abi.OCCLUSION_TARGETS if targets else 0, C.c_void_p(d_occluded_ptr or 0),
                                         C.c_void_p(d_mask_ptr or 0), C.c_void_p(d_stats_ptr or 0),
+                                        C.c_void_p(stream_ptr or 0)))
+
+    def radiance_rays(self, d_origins_ptr, d_directions_ptr, n_rays, d_sum_ptr=None, sample_begin=0, sample_count=1,
+                      bounce_max=50, seed=0xdeadbeef, ray_base=0, t_min=1e-3, t_max=INF, d_states_ptr=None,
+                      d_stats_ptr=None, ray_stride=3, stream_ptr=None):
+        """rt_radiance_rays: Camera.rayColor of n_rays rays on the device, bit for bit.  Rays as trace_rays.
+        Samples [sample_begin, sample_begin + sample_count) of ray q, each on the stream
+        rt_sample_key(seed, ray_base + q, s), are added in sample order to the unscaled sums d_sum_ptr
+        (n x 3 f64; sample_begin == 0 overwrites, > 0 continues).  d_states_ptr (n x 4 u64): the one
+        sample continues these Xoshiro256++ states instead (sample_count must be 1).  d_stats_ptr: 3 x
+        u64, incremented by {paths, segments, segments answered by the list scan}.  Always parity
+        arithmetic."""
+        prm = abi.RtRadianceParams(seed=seed, ray_base=ray_base, sample_begin=sample_begin, sample_count=sample_count,
+                                   bounce_max=bounce_max, reserved=0, t_min=t_min, t_max=t_max)
+        check("rt_radiance_rays",
+              self.lib.rt_radiance_rays(self.ctx, C.c_void_p(d_origins_ptr or 0), C.c_void_p(d_directions_ptr or 0),
+                                        ray_stride, n_rays, C.byref(prm), C.c_void_p(d_states_ptr or 0),
+                                        C.c_void_p(d_sum_ptr or 0), C.c_void_p(d_stats_ptr or 0),
                                         C.c_void_p(stream_ptr or 0)))
 
     def origin_bound(self):

@@ -6,8 +6,8 @@ render call goes through the HIP kernel on a gfx950 device (rt_render / rt_rende
 import ctypes as C
 import os
 
-from .abi import (RtCamera, RtCameraParams, RtDenoiseParams, RtOptions, RtRayHits, RtSphere, RtTemporalFrame,
-                  RtTemporalParams)
+from .abi import (RtCamera, RtCameraParams, RtDenoiseParams, RtOptions, RtRadianceParams, RtRayHits, RtSphere,
+                  RtTemporalFrame, RtTemporalParams)
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "librtzig.so")
@@ -33,6 +33,7 @@ EXPORTED = [
     "rt_temporal_accumulate",
     "rt_trace_rays",
     "rt_occluded_rays",
+    "rt_radiance_rays",
     "rt_context_origin_bound",
     "rt_context_reserve_origin_bound",
     "rt_context_flush",
@@ -105,6 +106,7 @@ def _declare(lib):
                                     vp, vp]),
         "rt_occluded_rays": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_double, C.c_double, vp, C.c_uint32,
                                        vp, vp, vp, vp]),
+        "rt_radiance_rays": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint64, P(RtRadianceParams), vp, vp, vp, vp]),
         "rt_context_origin_bound": (C.c_int, [vp, P(C.c_double)]),
         "rt_context_reserve_origin_bound": (C.c_int, [vp, C.c_double]),
         "rt_context_flush": (C.c_int, [vp]),

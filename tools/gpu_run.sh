@@ -39,6 +39,11 @@
 #              visibility, shadow rays and segments to a point light (tools/occlusion_cost.py; its JSON on
 #              stdout is kept as profiles/occlusion/cost.json).  Its GPU tests (tests/test_gpu_occlusion.py)
 #              run with the `tests` step
+#   radiance   what a radiance query costs against the renderer on the same paths: rt_radiance_rays at 16
+#              samples of 960,000 pixel-centre rays against rt_render_rows_accumulate, the one-sample,
+#              permuted and tiny-batch figures (tools/radiance_cost.py; its JSON on stdout is kept as
+#              profiles/radiance/cost.json).  Its GPU tests (tests/test_gpu_radiance.py) run with the
+#              `tests` step
 #   denoise   what rt_denoise costs against the 16-sample gather pass it stands in for, per level and
 #              kernel form, and the RMSE table against a 500-spp frame, on config 4's image
 #              (tools/denoise_cost.py; the "cost" and "quality" objects of its JSON on stdout are kept
@@ -87,6 +92,7 @@ for step in "$@"; do
     features) run features 200 python3 -u tools/feature_cost.py ;;
     trace)   run trace 300 python3 -u tools/trace_cost.py ;;
     occlusion) run occlusion 300 python3 -u tools/occlusion_cost.py ;;
+    radiance) run radiance 300 python3 -u tools/radiance_cost.py ;;
     denoise) run denoise 300 python3 -u tools/denoise_cost.py ;;
     temporal) run temporal 300 python3 -u tools/temporal_cost.py ;;
     peak)    run peak 300 ./tools/bin/peak_rates ${PEAK_MS:-60} ${PEAK_MODE:-2} ;;
